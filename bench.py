@@ -23,6 +23,13 @@ Production device path: one engine, steps alternating between two HIP streams (t
 workspace ring keeps two batches in flight, so one batch's scan fills the tail of the other's
 fingerprinting).  The one-stream rate is reported beside it (`one_stream`).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set up,
+clock ramp, W warmup steps, the N timed steps, the result line.  `--dump-outputs DIR` also writes
+what the last timed step computed (DIR/<name>.npy; the inputs are the same from run to run).
+`--full` adds every other leg to the line: the per-stage breakdown, the one-stream region and the
+roofline with its live VALU ceiling, the records' digests and self-checks, the other chunk mix,
+the host paths (batch call, caller-thread sweep) and the CPU baseline.
+
 Prints ONE JSON line on rank 0 (contract in the task statement); diagnostics go to stderr.
 """
 import argparse
@@ -134,6 +141,47 @@ def table_digest(torch, rows) -> str:
     import hashlib
 
     return hashlib.sha256(rows.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+DUMP_SEED = 0x5DF5D0
+DUMP_SLOT_BYTES = 40 << 20   # float32 budget of the per-slot arrays (starts, lens, digests)
+DUMP_RECORD_ROWS = 1 << 16   # rows of the record table kept (12 MiB as float32)
+
+
+def dump_outputs(torch, out_dir: str, batch, suffix: str = "") -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as .npy (float32
+    where every value is an integer below 2^24, float64 for the indices and the total, so all
+    exact): the chunk count of every buffer, the total,
+    and, for a fixed seeded sample of buffers, every slot's start, length and digest bytes (slots
+    past a buffer's count zeroed: the engine leaves them undefined), plus a fixed seeded sample of
+    the rows of the dense 48-byte record table.  Under 64 MB in all at any workload size."""
+    import numpy as np
+
+    torch.cuda.synchronize(batch.data.device)
+    os.makedirs(out_dir, exist_ok=True)
+    nbuf, cap = batch.nbuf, batch.cap
+    rng = np.random.default_rng(DUMP_SEED)
+    ns = max(1, min(nbuf, DUMP_SLOT_BYTES // (cap * 34 * 4)))
+    pick = np.sort(rng.choice(nbuf, ns, replace=False))
+    idx = torch.as_tensor(pick, device=batch.data.device)
+    counts = batch.counts.cpu().numpy().astype(np.int64)
+    total = int(batch.total.item())
+    valid = np.arange(cap)[None, :] < counts[pick][:, None]
+    out = {
+        "counts": counts,
+        "total": np.array([total]),
+        "sample_buffers": pick,
+        "starts": batch.starts.view(nbuf, cap)[idx].cpu().numpy() * valid,
+        "lens": batch.lens.view(nbuf, cap)[idx].cpu().numpy() * valid,
+        "digests": batch.digests.view(nbuf, cap, 32)[idx].cpu().numpy() * valid[:, :, None],
+    }
+    if batch.recs is not None and total > 0:
+        rows = np.sort(rng.choice(total, min(total, DUMP_RECORD_ROWS), replace=False))
+        out["record_rows"] = rows
+        out["records"] = batch.record_table()[torch.as_tensor(rows, device=batch.data.device)].cpu().numpy()
+    for name, a in out.items():
+        dt = np.float64 if name in ("total", "sample_buffers", "record_rows") else np.float32
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=dt))
 
 
 def exchange_check(torch, dist, gathered, counts, own_slot, total, rank, world, device) -> dict:
@@ -316,6 +364,28 @@ def threads_sweep(eng_cfg, device, host, buf_len, thread_counts, mode="fill"):
     eng.destroy()
     return out
 
+
+def headline_block(args, n: int, value: float, ms_step: float, config: dict) -> dict:
+    """The result line of a plain run; --full adds its legs to it."""
+    return {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": n,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (counter-based SplitMix64 streams, 0% duplicate), resident in HBM",
+        "full": bool(args.full),
+        "config": config,
+        "commit": git_head(),
+    }
+
+
 def main_device_set(args):
     """--gpus N > 1 without a launcher: ONE process, one engine whose device set is GPUs 0..N-1.
     GPU d owns streams [64d, 64d+64) (weak scaling, as one rank per GPU would), each GPU keeps two
@@ -391,12 +461,33 @@ def main_device_set(args):
     eng.set_timing(0)
     value = n * nbytes * args.steps / elapsed / 2**30
     ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        for d in range(n):
+            dump_outputs(torch, args.dump_outputs, batches[d][last % 2], f"_gpu{d}" if n > 1 else "")
+
+    counts, stride = ex.results[-1]
+    totals = [int(batches[d][last % 2].total.item()) for d in range(n)]
+    params = (f"P=0x26CE86126EF863 W=48 minLen={cfg.min_len} maxLen={cfg.max_len} "
+              f"pred=(fp&{cfg.pred_mask:#x})==0 n>minLen {args.hash_type}")
+    res = headline_block(args, n, value, ms_step, {
+        "workload": f"{args.streams} streams x {args.stream_mib} MiB per GPU, CHUNK_LENGTH {buf_len} B "
+                    f"({batches[0][0].nbuf} buffers, {nbytes / 2**30:.2f} GiB per GPU), fresh CDC state per buffer",
+        "params": params,
+        "mean_chunk_bytes": round(n * nbytes / max(sum(totals), 1), 1),
+        "chunks_per_gpu_step": totals,
+        "streams_in_flight": 2,
+        "exchange": "in-process RCCL all-gather of the 48-B fingerprint records by the engine "
+                    "(sdfs_cdc_allgather_records), pipelined one step behind production",
+        "parallelism": f"device set of {n} GPUs in one process (streams sharded per GPU)",
+    })
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        eng.destroy()
+        return
 
     # the exchanged table of the last timed step, checked: every device's count is its batch's
     # total, and device j's rows in GPU 0's gathered table are device j's own records
-    counts, stride = ex.results[-1]
     k_last = last % ex.nslots
-    totals = [int(batches[d][last % 2].total.item()) for d in range(n)]
     g0 = ex.gathered[0][last % 2]
     rows_match = all(
         torch.equal(g0[j * stride: j * stride + counts[j]].cpu(), ex.slots[j][k_last][: counts[j]].cpu())
@@ -424,40 +515,15 @@ def main_device_set(args):
     with torch.cuda.device(0):
         ceiling = sha_ceiling(0)  # right after the one-stream region: the same clock regime
         sha_blocks = sha_blocks_of(torch, batches[0][0])
-    params = (f"P=0x26CE86126EF863 W=48 minLen={cfg.min_len} maxLen={cfg.max_len} "
-              f"pred=(fp&{cfg.pred_mask:#x})==0 n>minLen {args.hash_type}")
     traffic, traffic_src = load_traffic("chunk_hash", params)
     roof = roofline_block(nbytes, hash_ms[0], ms_step, sha_blocks, ceiling, traffic, traffic_src,
                           "HIP events around chunk_hash on GPU 0's launch stream over a one-stream region of "
                           f"{args.steps} steps per GPU (stream-ordered: nothing overlaps the kernel)",
                           hash_ms_live[0])
     cpu = cpu_baseline_block(args, cfg) if args.cpu_secs > 0 else None
-    res = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "GiB/s",
-        "n_gpus": n,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (counter-based SplitMix64 streams, 0% duplicate), resident in HBM",
-        "config": {
-            "workload": f"{args.streams} streams x {args.stream_mib} MiB per GPU, CHUNK_LENGTH {buf_len} B "
-                        f"({batches[0][0].nbuf} buffers, {nbytes / 2**30:.2f} GiB per GPU), fresh CDC state per buffer",
-            "params": params,
-            "mean_chunk_bytes": round(n * nbytes / max(sum(totals), 1), 1),
-            "chunks_per_gpu_step": totals,
-            "streams_in_flight": 2,
-            "exchange": "in-process RCCL all-gather of the 48-B fingerprint records by the engine "
-                        "(sdfs_cdc_allgather_records), pipelined one step behind production",
-            "exchange_last_step": {"counts": counts, "stride": stride, "counts_match": counts == totals,
-                                   "rows_match": rows_match, "table_sha256": table_sha},
-            "parallelism": f"device set of {n} GPUs in one process (streams sharded per GPU)",
-        },
+    res["config"]["exchange_last_step"] = {"counts": counts, "stride": stride, "counts_match": counts == totals,
+                                           "rows_match": rows_match, "table_sha256": table_sha}
+    res.update({
         "kernels_ms": {"chunk_hash_per_gpu": [round(x, 4) for x in hash_ms],
                        "chunk_hash_two_stream_per_gpu": [round(x, 4) for x in hash_ms_live]},
         "one_stream": {"streams_in_flight": 1, "value": round(n * nbytes * args.steps / el_one / 2**30, 3),
@@ -465,8 +531,7 @@ def main_device_set(args):
         "roofline": roof,
         "records_sha256": table_digest(torch, batches[0][0].record_table()),
         "cpu_baseline": cpu,
-        "commit": git_head(),
-    }
+    })
     print(json.dumps(res), flush=True)
     eng.destroy()
 
@@ -476,6 +541,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (per-stage breakdown, one-stream region and roofline, record "
+                         "digests and self-checks, the other chunk mix, host paths, CPU baseline); the options "
+                         "below that size or switch those legs act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64, < 64 MB)")
     ap.add_argument("--streams", type=int, default=64, help="write streams per GPU")
     ap.add_argument("--stream-mib", type=int, default=64)
     ap.add_argument("--buf-kib", type=int, default=256, help="CHUNK_LENGTH in KiB")
@@ -657,6 +728,34 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     hash_ms_live = eng.kernel_times().get("chunk_hash", 0.0)
+    last_batch = runner.batches[(runner.k - 1) % len(runner.batches)] if nsf >= 2 else batch
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, last_batch, f"_gpu{rank}" if world > 1 else "")
+    value = world * nbytes * args.steps / elapsed / 2**30
+    ms_step = elapsed / args.steps * 1e3
+    params = (f"P=0x26CE86126EF863 W=48 minLen={cfg.min_len} maxLen={cfg.max_len} "
+              f"pred=(fp&{cfg.pred_mask:#x})==0 n>minLen {args.hash_type}")
+    total = int(last_batch.total.item())
+    res = headline_block(args, world, value, ms_step, {
+        "workload": f"{args.streams} streams x {args.stream_mib} MiB per GPU, CHUNK_LENGTH {buf_len} B "
+                    f"({nbuf} buffers, {nbytes / 2**30:.2f} GiB per GPU), fresh CDC state per buffer",
+        "params": params,
+        "mean_chunk_bytes": round(nbytes / max(total, 1), 1),
+        "chunks_per_gpu_step": total,
+        "streams_in_flight": nsf,
+        "exchange": (f"RCCL all_gather of 48-B fingerprint records, pipelined ({args.exchange_mode})"
+                     if use_ex else "none (N=1)"),
+        "parallelism": f"dp{world} (streams sharded per GPU)",
+    })
+    res["exchange_proxy"] = proxy_info
+    if not args.full:
+        eng.set_timing(0)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
     identical = runner.identical() if nsf >= 2 else None
 
     # per-stage breakdown (untimed, one stream, events around every kernel)
@@ -798,42 +897,15 @@ def main():
             dist.destroy_process_group()
         return
 
-    value = world * nbytes * args.steps / elapsed / 2**30
-    ms_step = elapsed / args.steps * 1e3
     # the roofline's kernel time cannot exceed the step it is part of
     assert 0 < hash_ms_one <= ms_step, f"chunk_hash {hash_ms_one:.3f} ms per launch > {ms_step:.3f} ms per step"
-    params = (f"P=0x26CE86126EF863 W=48 minLen={cfg.min_len} maxLen={cfg.max_len} "
-              f"pred=(fp&{cfg.pred_mask:#x})==0 n>minLen {args.hash_type}")
     traffic, traffic_src = load_traffic("chunk_hash", params)
     # the CPU restatement on rank 0's host share (the GPU box's CPU share is 16 cores per GPU;
     # the host's nproc shows the whole machine), after all GPU work
     cpu = cpu_baseline_block(args, cfg) if args.cpu_secs > 0 else None
-    res = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (counter-based SplitMix64 streams, 0% duplicate), resident in HBM",
-        "config": {
-            "workload": f"{args.streams} streams x {args.stream_mib} MiB per GPU, CHUNK_LENGTH {buf_len} B "
-                        f"({nbuf} buffers, {nbytes / 2**30:.2f} GiB per GPU), fresh CDC state per buffer",
-            "params": params,
-            "mean_chunk_bytes": round(nbytes / max(total, 1), 1),
-            "chunks_per_gpu_step": total,
-            "streams_in_flight": nsf,
-            "records_identical_across_streams": identical,
-            "exchange": (f"RCCL all_gather of 48-B fingerprint records, pipelined ({args.exchange_mode})"
-                         if use_ex else "none (N=1)"),
-            "exchange_last_step": ex_check,
-            "parallelism": f"dp{world} (streams sharded per GPU)",
-        },
+    res["config"]["records_identical_across_streams"] = identical
+    res["config"]["exchange_last_step"] = ex_check
+    res.update({
         "kernels_ms": {k: round(v, 4) for k, v in kt.items()},
         "kernels_note": "every stage: HIP events around each kernel in a separate untimed one-stream pass",
         "roofline": roofline_block(
@@ -842,7 +914,6 @@ def main():
             f"{args.steps} steps (stream-ordered: nothing overlaps the kernel)",
             hash_ms_live if nsf >= 2 else None),
         "chunk_hash_ms_per_rank": hash_ms_ranks,
-        "exchange_proxy": proxy_info,
         "records_sha256": records_sha,
         "cpu_baseline": cpu,
         ("one_stream" if nsf >= 2 else "two_streams"): other,
@@ -850,8 +921,7 @@ def main():
         "e2e_host_gibps": round(e2e, 3) if e2e else None,
         "e2e_pinned_host_gibps": round(e2e_pinned, 3) if e2e_pinned else None,
         "e2e_getchunks_threads": sweep,
-        "commit": git_head(),
-    }
+    })
     print(json.dumps(res), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -39,6 +39,6 @@ def test_cli_accepts_the_launch_forms():
     # --help parses every option; the forms themselves need a GPU (tests/test_bench_forms.py)
     r = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0
-    for opt in ("--gpus", "--steps", "--warmup", "--inproc", "--exchange", "--exchange-proxy", "--proxy-wgs",
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs", "--inproc", "--exchange", "--exchange-proxy", "--proxy-wgs",
                 "--proxy-gbps", "--proxy-record-bytes", "--proxy-prio", "--threads"):
         assert opt in r.stdout, opt
