@@ -66,9 +66,67 @@ int sdfs_cdc_index_get(sdfs_cdc_index* ix, const uint8_t* d_digests, uint64_t n,
 /* Drop every fingerprint (AbstractHashesMap.clear / a fresh map), enqueued on `stream`. */
 int sdfs_cdc_index_clear(sdfs_cdc_index* ix, void* stream);
 
-/* Fingerprints held (synchronises the index's last stream) and slot capacity.
+/* Fingerprints held (synchronises the index's last stream) and slot capacity.  Fingerprints whose
+ * count is <= 0 but which no sweep has removed yet are held.
  * (AbstractHashesMap.getSize / getMaxSize) */
 int sdfs_cdc_index_size(sdfs_cdc_index* ix, uint64_t* used, uint64_t* capacity);
+
+/* ---- releasing claims, collecting dead fingerprints, getting the space back ----
+ *
+ * The reference counts go both ways: DedupFileStore.removeRef (DedupFileStore.java:161-172) calls
+ * claimKey(hash, val, -ct) for every HashLocPair of a deleted file or an overwritten block, addRef
+ * (DedupFileStore.java:130-141) calls it with +ct for copies and snapshots (HCServiceProxy.claimKey
+ * -> HashStore.claimKey -> RocksDBMap.claimKey, RocksDBMap.java:388-509), and the collection pass
+ * RocksDBMap.claimRecords (RocksDBMap.java:630-714) removes what stayed unreferenced.
+ *
+ * One deliberate simplification.  RocksDBMap moves an entry whose count reaches <= 0 into a side
+ * table (rmdb) with a time stamp (RocksDBMap.java:401-406,431-437); claimRecords later recovers it if it
+ * was referenced again (RocksDBMap.java:663-680) or deletes it once it is older than
+ * Main.HT_RM_THRESH.  Here such an entry STAYS IN THE TABLE, still found by put_records, get and
+ * claim, with its count <= 0, until a sweep removes it: a put_records on it is a plain hit (dup =
+ * 1, the old pos, count += claims — the reference's "reclaimed" branch; the chunk's data still
+ * exists because nobody has been told to delete it).  There is no time stamp: the grace period
+ * (Main.HT_RM_THRESH) is the caller's sweep schedule — whatever is unreferenced WHEN the sweep
+ * runs is removed.  The count is a signed 64-bit value and is never clamped, so a batch's result
+ * does not depend on the order in which its items are applied.
+ *
+ * A swept slot becomes a tombstone: lookups step over it and never match its stale key.
+ * Fingerprints held plus tombstones count against the 7/8 fill.  When a put_records batch fits
+ * the fingerprints held but not those plus the tombstones, the table is rebuilt first, on the
+ * batch's stream (fingerprints held keep pos and count, tombstones go); only a batch that does
+ * not fit the fingerprints held returns SDFS_CDC_ECAP.  The rebuild goes through a transient
+ * second table allocated in stream order: it needs 64 x slots bytes of free device memory (as
+ * much as the index itself) for its duration and returns SDFS_CDC_ENOMEM, with the index
+ * unchanged, when that is not there.
+ */
+
+/* Add d_delta[i] (signed) to the count of fingerprint i (d_digests: n x 32 bytes, zero-padded) if
+ * it is present and, when d_expect_pos != NULL and d_expect_pos[i] != UINT64_MAX, its pos equals
+ * d_expect_pos[i]: d_out_pos[i] = its pos.  Otherwise nothing changes and d_out_pos[i] =
+ * UINT64_MAX (the reference's -1: key not found or wrong archive).  Items with the same digest
+ * all apply.  d_out_pos may be NULL.
+ * (AbstractHashesMap.claimKey(hash, val, ct), RocksDBMap.java:388-509) */
+int sdfs_cdc_index_claim(sdfs_cdc_index* ix, const uint8_t* d_digests, const uint64_t* d_expect_pos,
+                         const int64_t* d_delta, uint64_t n, uint64_t* d_out_pos, void* stream);
+
+/* Remove fingerprints whose count is <= 0: the first `cap` of them in slot order become
+ * tombstones and their {digest[32], pos} are written to d_removed_digests / d_removed_pos (cap
+ * entries each, order unspecified; may be NULL when cap = 0); the rest stay for the next call.
+ * d_counts[0] = removed, d_counts[1] = dead fingerprints left behind (device, u64[2]).  The
+ * caller tells the chunk store to drop the removed positions.
+ * (AbstractHashesMap.claimRecords, RocksDBMap.java:630-714; see the note above on rmdb and
+ * Main.HT_RM_THRESH) */
+int sdfs_cdc_index_sweep(sdfs_cdc_index* ix, uint8_t* d_removed_digests, uint64_t* d_removed_pos,
+                         uint64_t cap, uint64_t* d_counts, void* stream);
+
+/* Rebuild the table now, on `stream`: fingerprints held keep pos and count, tombstones go.
+ * Needs 64 x slots bytes of free device memory (SDFS_CDC_ENOMEM otherwise, index unchanged).
+ * (the `compact` flag of RocksDBMap.claimRecords, RocksDBMap.java:697-708) */
+int sdfs_cdc_index_compact(sdfs_cdc_index* ix, void* stream);
+
+/* Fingerprints held, tombstones, and slot capacity (synchronises the index's last stream); any
+ * output may be NULL.  (AbstractHashesMap.getSize / getMaxSize) */
+int sdfs_cdc_index_stats(sdfs_cdc_index* ix, uint64_t* live, uint64_t* tombstones, uint64_t* capacity);
 
 /* Test hook: the batch epoch counter (31 bits; the next put_records uses epoch + 1, wrapping to 1).
  * Stamps only mark a batch's own insertions while it runs, so any value is safe. */

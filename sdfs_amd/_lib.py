@@ -133,6 +133,10 @@ SIGNATURES = {
     "sdfs_cdc_index_size": (ctypes.c_int, [_vp, _u64p, _u64p]),
     "sdfs_cdc_index_clear": (ctypes.c_int, [_vp, _vp]),
     "sdfs_cdc_index_set_epoch": (ctypes.c_int, [_vp, ctypes.c_uint32]),
+    "sdfs_cdc_index_claim": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_index_sweep": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_index_compact": (ctypes.c_int, [_vp, _vp]),
+    "sdfs_cdc_index_stats": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p]),
     # include/sdfs_lz4.h
     "sdfs_cdc_lz4_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
     "sdfs_cdc_lz4_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P(_vp)]),

@@ -25,6 +25,15 @@
 //   6. output  — per record: dup = not inserted, hashloc = its fingerprint's pos.
 // The outcome is what applying the batch's buffers one after another gives (the first record of
 // a new fingerprint is the inserted one), independent of the GPU's schedule.
+//
+// The other direction (removeRef / addRef -> claimKey, RocksDBMap.java:388-509; the claimRecords
+// collection pass, RocksDBMap.java:630-714): a claim adds a signed delta to a fingerprint's count;
+// an entry whose count is <= 0 stays in the table, findable, until a sweep turns it into a
+// tombstone (count / scan / emit over the slots, so the caller's cap is exact and the outcome
+// depends on the table alone).  Probes step over tombstones and never compare their stale keys.
+// Tombstones count against the fill; a rebuild copies the committed slots into a transient second
+// table (one CAS on `state` per entry, no key compares: all keys are distinct) and back.  Every
+// phase that reads what another workgroup wrote is its own kernel on the same stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,15 +50,17 @@ namespace {
 struct alignas(64) IndexSlot {
     uint4 key[2];     // digest, zero-padded to 32 bytes
     uint64_t pos;     // where the chunk lives (caller's namespace)
-    uint64_t ref;     // reference count
-    uint32_t state;   // 0 = empty, kCommitted = holds a fingerprint, (epoch << 1) | 1 (epoch >= 1) =
-                      // being inserted by the batch of that epoch
+    uint64_t ref;     // reference count (signed: claims may take it to 0 or below)
+    uint32_t state;   // 0 = empty, kCommitted = holds a fingerprint, kTombstone = swept (the key is
+                      // stale; probes step over it), (epoch << 1) | 1 (epoch >= 1) = being inserted
+                      // by the batch of that epoch
     uint32_t pad[3];
 };
 static_assert(sizeof(IndexSlot) == 64, "one cache line per slot");
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kCommitted = 1u;  // never a batch stamp: those are >= 3
+constexpr uint32_t kTombstone = 2u;  // even: never a batch stamp either
 constexpr int kIxThreads = 256;
 constexpr int kRankBlock = 1024;
 
@@ -137,6 +148,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_probe_kernel(const uint8_t* rec
             st = old;
         }
         if (st == stamp) continue;  // inserted by this batch: a different fingerprint
+        if (st == kTombstone) continue;  // swept: the chain goes on, the key is stale
         if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
             atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)claims);
             gidx[ls] = (uint32_t)h;
@@ -254,7 +266,9 @@ __global__ __launch_bounds__(kIxThreads) void ix_get_kernel(const uint8_t* diges
     uint64_t rp = ~0ull, rr = 0;
     for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
         const IndexSlot& s = table[h];
-        if (s.state == 0) break;
+        const uint32_t st = s.state;
+        if (st == 0) break;
+        if (st == kTombstone) continue;
         if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
             rp = s.pos;
             rr = s.ref;
@@ -263,6 +277,120 @@ __global__ __launch_bounds__(kIxThreads) void ix_get_kernel(const uint8_t* diges
     }
     if (pos) pos[i] = rp;
     if (ref) ref[i] = rr;
+}
+
+// claim: ref += delta for a fingerprint that is present (and at expect_pos, when one is given)
+__global__ __launch_bounds__(kIxThreads) void ix_claim_kernel(const uint8_t* digests, const uint64_t* expect_pos,
+                                                              const int64_t* delta, uint64_t n, IndexSlot* table,
+                                                              uint64_t cmask, uint64_t* out_pos) {
+    const uint64_t i = (uint64_t)blockIdx.x * kIxThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint4* p = reinterpret_cast<const uint4*>(digests + i * 32);
+    const uint4 a = p[0], b = p[1];
+    const uint64_t want = expect_pos ? expect_pos[i] : ~0ull;
+    uint64_t h = mix64((uint64_t)a.y << 32 | a.x) & cmask;
+    uint64_t rp = ~0ull;
+    for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
+        IndexSlot& s = table[h];
+        const uint32_t st = s.state;
+        if (st == 0) break;
+        if (st == kTombstone) continue;
+        if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
+            const uint64_t pos = s.pos;
+            if (want == ~0ull || want == pos) {
+                atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)delta[i]);
+                rp = pos;
+            }
+            break;
+        }
+    }
+    if (out_pos) out_pos[i] = rp;
+}
+
+__device__ __forceinline__ uint32_t slot_is_dead(const IndexSlot* table, uint64_t slots, uint64_t i) {
+    return i < slots && table[i].state == kCommitted && (int64_t)table[i].ref <= 0 ? 1u : 0u;
+}
+
+// sweep 1. dead entries (committed, count <= 0) per block of kRankBlock consecutive slots; one
+// lane per slot, so a wave reads 64 contiguous slots; it leaves their dead flags as one 64-bit
+// word, and the emit pass does not have to stream the table a second time
+__global__ __launch_bounds__(kRankBlock) void ix_sweep_count_kernel(const IndexSlot* table, uint64_t slots,
+                                                                    uint32_t* bsum, unsigned long long* dead) {
+    __shared__ uint32_t lds[64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
+    const uint32_t f = slot_is_dead(table, slots, i);
+    const unsigned long long m = __ballot(f);
+    if ((threadIdx.x & 63) == 0) dead[i >> 6] = m;
+    uint32_t total;
+    (void)block_exclusive_scan(f, lds, total);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// sweep 2. exclusive scan of the block counts (one block); removed / left-behind counts; the
+// device's live and tombstone counts follow
+__global__ __launch_bounds__(kRankBlock) void ix_sweep_scan_kernel(uint32_t* bsum, uint32_t nblocks, uint64_t cap,
+                                                                   uint64_t* counts, uint64_t* used) {
+    __shared__ uint32_t lds[64];
+    uint64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += kRankBlock) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t v = i < nblocks ? bsum[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, lds, total);
+        if (i < nblocks) bsum[i] = (uint32_t)carry + ex;  // dead entries <= slots <= 2^31
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        const uint64_t removed = carry < cap ? carry : cap;
+        counts[0] = removed;
+        counts[1] = carry - removed;
+        used[0] -= removed;
+        used[1] += removed;
+    }
+}
+
+// sweep 3. the first `cap` dead entries in slot order: {digest, pos} -> removed list, slot -> tombstone
+__global__ __launch_bounds__(kRankBlock) void ix_sweep_emit_kernel(IndexSlot* table, uint64_t slots,
+                                                                   const uint32_t* bbase,
+                                                                   const unsigned long long* dead, uint64_t cap,
+                                                                   uint8_t* removed_digests, uint64_t* removed_pos) {
+    __shared__ uint32_t lds[64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
+    const uint32_t f = (uint32_t)(dead[i >> 6] >> (threadIdx.x & 63)) & 1u;  // set only for i < slots
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    if (!f) return;
+    const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
+    if (rank >= cap) return;
+    IndexSlot& s = table[i];
+    uint4* d = reinterpret_cast<uint4*>(removed_digests + rank * 32);
+    d[0] = s.key[0];
+    d[1] = s.key[1];
+    removed_pos[rank] = s.pos;
+    s.state = kTombstone;
+}
+
+// rebuild: every committed slot of `from` claims an empty slot of `to` (zeroed) with a CAS on its
+// state and writes its fields; keys are distinct, so lanes only step over occupied slots
+__global__ __launch_bounds__(kIxThreads) void ix_rebuild_kernel(const IndexSlot* from, IndexSlot* to,
+                                                                uint64_t slots) {
+    const uint64_t i = (uint64_t)blockIdx.x * kIxThreads + threadIdx.x;
+    if (i >= slots) return;
+    const IndexSlot& s = from[i];
+    if (s.state != kCommitted) return;
+    const uint4 a = s.key[0], b = s.key[1];
+    const uint64_t cmask = slots - 1;
+    uint64_t h = mix64((uint64_t)a.y << 32 | a.x) & cmask;
+    for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
+        IndexSlot& t = to[h];
+        if (t.state != 0) continue;
+        if (atomicCAS(&t.state, 0u, kCommitted) != 0) continue;
+        t.key[0] = a;
+        t.key[1] = b;
+        t.pos = s.pos;
+        t.ref = s.ref;
+        return;
+    }
 }
 
 template <typename T>
@@ -300,11 +428,17 @@ struct sdfs_cdc_index {
     int device = 0;
     uint64_t slots = 0;     // power of two
     uint64_t max_fill = 0;  // 7/8 of slots
-    uint64_t used_ub = 0;   // host-side upper bound of the fingerprints held
+    // host-side bounds: used_ub + tomb_ub is an upper bound of the occupied slots (fingerprints held
+    // plus tombstones).  A sweep moves entries from the first count to the second on the device
+    // only, which leaves the sum a bound; both are refreshed together from the device counts.
+    uint64_t used_ub = 0;
+    uint64_t tomb_ub = 0;
     uint32_t epoch = 0;
     IxBuf<IndexSlot> table;
-    IxBuf<uint64_t> used;  // [1] device count of fingerprints held
+    IxBuf<uint64_t> used;  // device counts: [0] fingerprints held, [1] tombstones
     IxBuf<uint32_t> ltab, lcount, lslot, gidx, isnew, bsum, overflow;
+    IxBuf<uint32_t> sweep_bsum;  // dead entries per kRankBlock slots (allocated with the table)
+    IxBuf<unsigned long long> sweep_dead;  // the slots' dead flags, one word per 64 slots (likewise)
     hipStream_t own = nullptr;   // the index's own non-blocking stream: set-up and readbacks
     hipStream_t last = nullptr;  // the stream of the latest batch (own until one comes)
     StreamOrder order;  // batches apply in call order whatever streams they come on
@@ -318,6 +452,51 @@ struct sdfs_cdc_index {
             return fail_status(SDFS_CDC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
                                __FILE__, __LINE__);                                                   \
     } while (0)
+
+// Both device counts (fingerprints held, tombstones) after everything enqueued so far; refreshes
+// the host-side bounds.  The caller holds ix->mu.
+static int read_counts(sdfs_cdc_index* ix, uint64_t* used, uint64_t* tombs, uint32_t* ovf) {
+    IX_TRY(hipStreamSynchronize(ix->last));
+    uint64_t c[2] = {0, 0};
+    uint32_t o = 0;
+    IX_TRY(hipMemcpyAsync(c, ix->used.p, sizeof(c), hipMemcpyDeviceToHost, ix->own));
+    IX_TRY(hipMemcpyAsync(&o, ix->overflow.p, sizeof(o), hipMemcpyDeviceToHost, ix->own));
+    IX_TRY(hipStreamSynchronize(ix->own));
+    ix->used_ub = c[0];
+    ix->tomb_ub = c[1];
+    *used = c[0];
+    *tombs = c[1];
+    if (ovf) *ovf = o;
+    return SDFS_CDC_OK;
+}
+
+// Enqueue a rebuild on s: committed slots -> a transient second table (stream-ordered allocation:
+// no null-stream work, no device-wide synchronisation) -> back into the index's table, whose
+// address stays what it was.  The caller holds ix->mu and has joined the order chain on s.
+// Nothing is enqueued before the allocation has succeeded, so ENOMEM leaves the index intact.
+static int rebuild_on(sdfs_cdc_index* ix, hipStream_t s) {
+    const size_t bytes = ix->slots * sizeof(IndexSlot);
+    IndexSlot* tmp = nullptr;
+    if (hipMallocAsync(reinterpret_cast<void**>(&tmp), bytes, s) != hipSuccess || !tmp) {
+        (void)hipGetLastError();
+        return fail_status(SDFS_CDC_ENOMEM, "index rebuild needs %llu bytes of free device memory",
+                           (unsigned long long)bytes);
+    }
+    hipError_t e = hipMemsetAsync(tmp, 0, bytes, s);
+    if (e == hipSuccess) {
+        const uint64_t g = (ix->slots + kIxThreads - 1) / kIxThreads;
+        hipLaunchKernelGGL(ix_rebuild_kernel, dim3((uint32_t)g), dim3(kIxThreads), 0, s, ix->table.p, tmp,
+                           ix->slots);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ix->table.p, tmp, bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(ix->used.p + 1, 0, sizeof(uint64_t), s);
+    const hipError_t ef = hipFreeAsync(tmp, s);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail_status(SDFS_CDC_EHIP, "index rebuild failed: %s", hipGetErrorString(e));
+    ix->tomb_ub = 0;
+    return SDFS_CDC_OK;
+}
 
 extern "C" {
 
@@ -339,8 +518,10 @@ int sdfs_cdc_index_create(int device, uint64_t capacity, sdfs_cdc_index** out) {
     ix->last = ix->own;
     ix->slots = next_pow2(capacity + capacity / 7 + 1);
     ix->max_fill = ix->slots - ix->slots / 8;
-    if (ix->table.ensure(ix->slots) != hipSuccess || ix->used.ensure(1) != hipSuccess ||
-        ix->overflow.ensure(1) != hipSuccess) {
+    if (ix->table.ensure(ix->slots) != hipSuccess || ix->used.ensure(2) != hipSuccess ||
+        ix->overflow.ensure(1) != hipSuccess ||
+        ix->sweep_bsum.ensure((ix->slots + kRankBlock - 1) / kRankBlock) != hipSuccess ||
+        ix->sweep_dead.ensure((ix->slots + kRankBlock - 1) / kRankBlock * (kRankBlock / 64)) != hipSuccess) {
         sdfs_cdc_index_destroy(ix);
         return fail_status(SDFS_CDC_ENOMEM, "index allocation (%llu slots) failed",
                            (unsigned long long)ix->slots);
@@ -348,7 +529,7 @@ int sdfs_cdc_index_create(int device, uint64_t capacity, sdfs_cdc_index** out) {
     // Nothing here or below runs on the legacy null stream or synchronises the device: the CDC
     // queue's lanes are blocking streams, and a null-stream operation would wait for their passes.
     if (hipMemsetAsync(ix->table.p, 0, ix->slots * sizeof(IndexSlot), ix->own) != hipSuccess ||
-        hipMemsetAsync(ix->used.p, 0, sizeof(uint64_t), ix->own) != hipSuccess ||
+        hipMemsetAsync(ix->used.p, 0, 2 * sizeof(uint64_t), ix->own) != hipSuccess ||
         hipMemsetAsync(ix->overflow.p, 0, sizeof(uint32_t), ix->own) != hipSuccess ||
         hipStreamSynchronize(ix->own) != hipSuccess) {
         sdfs_cdc_index_destroy(ix);
@@ -367,8 +548,10 @@ int sdfs_cdc_index_destroy(sdfs_cdc_index* ix) {
     if (ix->own) (void)hipStreamSynchronize(ix->own);
     ix->table.release();
     ix->used.release();
-    for (auto* b : {&ix->ltab, &ix->lcount, &ix->lslot, &ix->gidx, &ix->isnew, &ix->bsum, &ix->overflow})
+    for (auto* b : {&ix->ltab, &ix->lcount, &ix->lslot, &ix->gidx, &ix->isnew, &ix->bsum, &ix->overflow,
+                    &ix->sweep_bsum})
         b->release();
+    ix->sweep_dead.release();
     ix->order.destroy();
     if (ix->own) (void)hipStreamDestroy(ix->own);
     delete ix;
@@ -385,23 +568,27 @@ int sdfs_cdc_index_put_records(sdfs_cdc_index* ix, const uint8_t* d_records, uin
     std::lock_guard<std::mutex> lk(ix->mu);
     IX_TRY(hipSetDevice(ix->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (ix->used_ub + n_max > ix->max_fill) {  // refresh the bound from the device count
-        IX_TRY(hipStreamSynchronize(ix->last));
+    bool rebuild = false;
+    if (ix->used_ub + ix->tomb_ub + n_max > ix->max_fill) {  // refresh the bounds from the device counts
         IX_TRY(hipStreamSynchronize(s));
-        uint64_t used = 0;
+        uint64_t used = 0, tombs = 0;
         uint32_t ovf = 0;
-        IX_TRY(hipMemcpyAsync(&used, ix->used.p, sizeof(used), hipMemcpyDeviceToHost, ix->own));
-        IX_TRY(hipMemcpyAsync(&ovf, ix->overflow.p, sizeof(ovf), hipMemcpyDeviceToHost, ix->own));
-        IX_TRY(hipStreamSynchronize(ix->own));
+        const int rc = read_counts(ix, &used, &tombs, &ovf);
+        if (rc != SDFS_CDC_OK) return rc;
         if (ovf) return fail_status(SDFS_CDC_ECAP, "index overflowed");
-        ix->used_ub = used;
         if (used + n_max > ix->max_fill)
             return fail_status(SDFS_CDC_ECAP, "index full: %llu of %llu fingerprints held, batch of %llu",
                                (unsigned long long)used, (unsigned long long)ix->max_fill,
                                (unsigned long long)n_max);
+        // the batch fits the fingerprints held but not those plus the tombstones: drop them first
+        rebuild = used + tombs + n_max > ix->max_fill;
     }
     IX_TRY(ix->order.acquire(s));
     ix->last = s;
+    if (rebuild) {
+        const int rc = rebuild_on(ix, s);
+        if (rc != SDFS_CDC_OK) return rc;
+    }
     if (n_max == 0) {
         IX_TRY(hipMemsetAsync(d_new_count, 0, sizeof(uint64_t), s));
         IX_TRY(ix->order.release(s));
@@ -463,11 +650,80 @@ int sdfs_cdc_index_clear(sdfs_cdc_index* ix, void* stream) {
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     IX_TRY(ix->order.acquire(s));
     IX_TRY(hipMemsetAsync(ix->table.p, 0, ix->slots * sizeof(IndexSlot), s));
-    IX_TRY(hipMemsetAsync(ix->used.p, 0, sizeof(uint64_t), s));
+    IX_TRY(hipMemsetAsync(ix->used.p, 0, 2 * sizeof(uint64_t), s));
     IX_TRY(hipMemsetAsync(ix->overflow.p, 0, sizeof(uint32_t), s));
     IX_TRY(ix->order.release(s));
     ix->used_ub = 0;
+    ix->tomb_ub = 0;
     ix->last = s;
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_claim(sdfs_cdc_index* ix, const uint8_t* d_digests, const uint64_t* d_expect_pos,
+                         const int64_t* d_delta, uint64_t n, uint64_t* d_out_pos, void* stream) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    if (n && !d_digests) return fail_status(SDFS_CDC_EINVAL, "null digests");
+    if (n && !d_delta) return fail_status(SDFS_CDC_EINVAL, "null delta");
+    if (n >= (1ull << 31) * kIxThreads) return fail_status(SDFS_CDC_EINVAL, "batch too large");
+    if (n == 0) return SDFS_CDC_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    const uint64_t g = (n + kIxThreads - 1) / kIxThreads;
+    hipLaunchKernelGGL(ix_claim_kernel, dim3((uint32_t)g), dim3(kIxThreads), 0, s, d_digests, d_expect_pos, d_delta, n,
+                       ix->table.p, ix->slots - 1, d_out_pos);
+    IX_TRY(hipGetLastError());
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_sweep(sdfs_cdc_index* ix, uint8_t* d_removed_digests, uint64_t* d_removed_pos, uint64_t cap,
+                         uint64_t* d_counts, void* stream) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    if (!d_counts) return fail_status(SDFS_CDC_EINVAL, "null counts");
+    if (cap && (!d_removed_digests || !d_removed_pos)) return fail_status(SDFS_CDC_EINVAL, "null removed list");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    const uint32_t nb = (uint32_t)((ix->slots + kRankBlock - 1) / kRankBlock);
+    hipLaunchKernelGGL(ix_sweep_count_kernel, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                       ix->sweep_bsum.p, ix->sweep_dead.p);
+    hipLaunchKernelGGL(ix_sweep_scan_kernel, dim3(1), dim3(kRankBlock), 0, s, ix->sweep_bsum.p, nb, cap, d_counts,
+                       ix->used.p);
+    hipLaunchKernelGGL(ix_sweep_emit_kernel, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                       ix->sweep_bsum.p, ix->sweep_dead.p, cap, d_removed_digests, d_removed_pos);
+    IX_TRY(hipGetLastError());
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_compact(sdfs_cdc_index* ix, void* stream) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    const int rc = rebuild_on(ix, s);
+    if (rc != SDFS_CDC_OK) return rc;
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_stats(sdfs_cdc_index* ix, uint64_t* live, uint64_t* tombstones, uint64_t* capacity) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    uint64_t u = 0, t = 0;
+    const int rc = read_counts(ix, &u, &t, nullptr);
+    if (rc != SDFS_CDC_OK) return rc;
+    if (live) *live = u;
+    if (tombstones) *tombstones = t;
+    if (capacity) *capacity = ix->max_fill;
     return SDFS_CDC_OK;
 }
 
@@ -482,11 +738,9 @@ int sdfs_cdc_index_size(sdfs_cdc_index* ix, uint64_t* used, uint64_t* capacity) 
     if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
     std::lock_guard<std::mutex> lk(ix->mu);
     IX_TRY(hipSetDevice(ix->device));
-    IX_TRY(hipStreamSynchronize(ix->last));
-    uint64_t u = 0;
-    IX_TRY(hipMemcpyAsync(&u, ix->used.p, sizeof(u), hipMemcpyDeviceToHost, ix->own));
-    IX_TRY(hipStreamSynchronize(ix->own));
-    ix->used_ub = u;
+    uint64_t u = 0, t = 0;
+    const int rc = read_counts(ix, &u, &t, nullptr);
+    if (rc != SDFS_CDC_OK) return rc;
     if (used) *used = u;
     if (capacity) *capacity = ix->max_fill;
     return SDFS_CDC_OK;

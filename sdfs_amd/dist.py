@@ -219,7 +219,8 @@ def shard_of(records: torch.Tensor, world: int, hash_len: int = 32) -> torch.Ten
 
 class ShardedDedupIndex:
     """The dedup-hit index split across ranks by fingerprint: every rank owns one shard (its
-    ``index``: a HipHashesMap, or any object with the same ``put_records``).
+    ``index``: a HipHashesMap, or any object with the same ``put_records``, ``claim_digests`` and
+    ``sweep``).
 
     ``put_records(table, count)`` — this rank's fingerprint records (e.g. its engine's record
     table) — routes every record to its owner with one all-to-all, applies them there in
@@ -269,6 +270,50 @@ class ShardedDedupIndex:
         out_dup[order] = back_dup
         out_loc[order] = back_loc
         return out_dup, out_loc
+
+    def claim_digests(self, digests: torch.Tensor, delta, expect_pos=None):
+        """``HipHashesMap.claim_digests`` across the shards (removeRef / addRef -> claimKey): this
+        rank's items (digests u8[n, 32], delta int64[n] or one int, expect_pos int64[n] with -1 =
+        any, or None) travel to their owners with one all-to-all as 48-byte rows {digest, delta,
+        expect_pos}, are applied there in (source rank, item) order, and each item's pos (-1:
+        nothing claimed) comes back with a second one, in the caller's order."""
+        dev = digests.device
+        n = int(digests.shape[0])
+        if not isinstance(delta, torch.Tensor):
+            delta = torch.full((n,), int(delta), dtype=torch.int64, device=dev)
+        if expect_pos is None:
+            expect_pos = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        rows = torch.empty(n, RECORD_BYTES, dtype=torch.uint8, device=dev)
+        rows[:, :32] = digests
+        rows[:, 32:40] = delta.to(device=dev, dtype=torch.int64).contiguous().view(torch.uint8).view(n, 8)
+        rows[:, 40:48] = expect_pos.to(device=dev, dtype=torch.int64).contiguous().view(torch.uint8).view(n, 8)
+        owner = shard_of(rows, self.world, self.hash_len) if n else torch.zeros(0, dtype=torch.int64, device=dev)
+        order = torch.argsort(owner, stable=True)
+        send = rows[order].contiguous()
+        send_counts = torch.bincount(owner, minlength=self.world).to(torch.int64)
+        recv_counts = torch.empty_like(send_counts)
+        dist.all_to_all_single(recv_counts, send_counts, group=self.group)
+        sc, rc = send_counts.tolist(), recv_counts.tolist()
+        recv = torch.empty(sum(rc), RECORD_BYTES, dtype=torch.uint8, device=dev)
+        dist.all_to_all_single(recv, send, output_split_sizes=rc, input_split_sizes=sc, group=self.group)
+        m = recv.shape[0]
+        if m:
+            pos = self.index.claim_digests(recv[:, :32].contiguous(),
+                                           recv[:, 32:40].contiguous().view(torch.int64).view(m),
+                                           recv[:, 40:48].contiguous().view(torch.int64).view(m))
+        else:
+            pos = torch.zeros(0, dtype=torch.int64, device=dev)
+        back = torch.empty(n, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(back, pos.contiguous(), output_split_sizes=sc, input_split_sizes=rc,
+                               group=self.group)
+        out = torch.empty_like(back)
+        out[order] = back
+        return out
+
+    def sweep(self, cap=None):
+        """The collection pass (claimRecords): every rank sweeps its own shard; no exchange.
+        Returns this shard's (digests, pos, left_behind) as ``HipHashesMap.sweep`` does."""
+        return self.index.sweep(cap)
 
 
 # ---- one process driving a device set (include/sdfs_cdc.h "Devices") ------------------------

@@ -5,7 +5,11 @@ with its claim count, and mark every chunk duplicate or new with its hashloc
 
 :class:`HipHashesMap` mirrors the parts of ``org.opendedup.collections.AbstractHashesMap`` this
 step uses (``put`` -> ``InsertRecord``, ``get``, ``containsKey``, ``getSize``, ``getMaxSize``) for a
-whole batch of fingerprint records at once.  No CPU fallback: it needs the HIP library and a
+whole batch of fingerprint records at once, and the way back: ``claimKey`` with a negative or
+positive count (DedupFileStore.removeRef / addRef, DedupFileStore.java:130-141,161-172;
+RocksDBMap.claimKey, RocksDBMap.java:388-509) and ``claimRecords``, the collection pass
+(RocksDBMap.java:630-714).  An unreferenced fingerprint stays in the index, findable, until a
+sweep removes it (include/sdfs_index.h).  No CPU fallback: it needs the HIP library and a
 gfx950 device.
 """
 from __future__ import annotations
@@ -22,6 +26,16 @@ class InsertRecord:
 
     inserted: bool
     pos: int
+
+
+@dataclass
+class IndexStats:
+    """Fingerprints held (unreferenced ones not yet swept included), tombstones left by sweeps,
+    and the number of slots that may be filled (both count against it)."""
+
+    live: int
+    tombstones: int
+    capacity: int
 
 
 class HipHashesMap:
@@ -79,7 +93,93 @@ class HipHashesMap:
                                                     ref.data_ptr(), s))
         return pos, ref
 
+    def claim_digests(self, digests, delta, expect_pos=None, stream=None):
+        """AbstractHashesMap.claimKey for a batch (RocksDBMap.java:388-509): add ``delta`` (device
+        int64[n], or one int for every item) to the count of each digest (torch uint8 [n, 32] on
+        the device) that is present and, where ``expect_pos`` (device int64[n], -1 = any) names
+        one, lives at that position.  Returns pos int64[n], -1 where nothing was claimed.
+        Enqueued on ``stream`` (default: torch's current stream; an int ``delta`` is expanded on
+        torch's current stream, so pass a tensor when ``stream`` is another one)."""
+        import torch
+
+        n = int(digests.shape[0])
+        dev = digests.device
+        pos = torch.empty(n, dtype=torch.int64, device=dev)
+        if n:
+            if not isinstance(delta, torch.Tensor):
+                delta = torch.full((n,), int(delta), dtype=torch.int64, device=dev)
+            delta = delta.to(device=dev, dtype=torch.int64).contiguous()
+            if delta.shape[0] != n:
+                raise ValueError("one delta per digest")
+            if expect_pos is not None:
+                expect_pos = expect_pos.to(device=dev, dtype=torch.int64).contiguous()
+                if expect_pos.shape[0] != n:
+                    raise ValueError("one expected position per digest")
+            digests = digests.contiguous()
+            s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self._lib.sdfs_cdc_index_claim(
+                self._h, digests.data_ptr(), expect_pos.data_ptr() if expect_pos is not None else None,
+                delta.data_ptr(), n, pos.data_ptr(), s))
+        return pos
+
+    def sweep(self, cap=None, stream=None):
+        """AbstractHashesMap.claimRecords (RocksDBMap.java:630-714): remove up to ``cap`` (default:
+        all) fingerprints whose count is <= 0.  Returns (digests u8[k, 32], pos int64[k] — what
+        the chunk store may now drop, in no particular order — and the number of dead
+        fingerprints left behind).  Waits for the sweep to finish (k comes from the device)."""
+        if cap is None:
+            cap = self.stats().live
+        digests, pos, counts = self.sweep_device(int(cap), stream)
+        self.stats()  # synchronises the sweep's stream
+        k, left = (int(v) for v in counts.tolist())
+        return digests[:k], pos[:k], left
+
+    def sweep_device(self, cap: int, stream=None):
+        """:meth:`sweep` without the wait: enqueues the sweep on ``stream`` (default, and where
+        given the stream torch is currently on: the outputs are allocated there) and returns the
+        device tensors (digests u8[cap, 32], pos int64[cap], counts int64[2] = removed, left
+        behind); the first counts[0] rows are valid once the stream has got there."""
+        import torch
+
+        dev = torch.device(f"cuda:{self.device}")
+        digests = torch.empty(max(cap, 1), 32, dtype=torch.uint8, device=dev)
+        pos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.sdfs_cdc_index_sweep(self._h, digests.data_ptr(), pos.data_ptr(), int(cap),
+                                                  counts.data_ptr(), s))
+        return digests, pos, counts
+
+    def compact(self, stream=None) -> None:
+        """Rebuild the table now, dropping the tombstones (needs as much free device memory as
+        the index holds; put_records does this by itself when a batch would not fit otherwise)."""
+        import torch
+
+        s = stream if stream is not None else torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.sdfs_cdc_index_compact(self._h, s))
+
+    def stats(self) -> "IndexStats":
+        live, tomb, cap = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._lib.sdfs_cdc_index_stats(self._h, ctypes.byref(live), ctypes.byref(tomb),
+                                                  ctypes.byref(cap)))
+        return IndexStats(live.value, tomb.value, cap.value)
+
     # --- AbstractHashesMap-style conveniences (host bytes) -------------------------------------
+    def claimKey(self, key: bytes, val: int, ct: int) -> int:
+        """AbstractHashesMap.claimKey(hash, val, ct): add ct (negative: DedupFileStore.removeRef,
+        positive: addRef) to the count of ``key`` if it lives at ``val`` (-1: wherever it lives);
+        its pos, or -1."""
+        import torch
+
+        expect = torch.tensor([int(val)], dtype=torch.int64, device=f"cuda:{self.device}")
+        return int(self.claim_digests(self._digest_tensor([key]), int(ct), expect)[0].item())
+
+    def claimRecords(self) -> list:
+        """AbstractHashesMap.claimRecords: remove every unreferenced fingerprint; [(digest, pos)]."""
+        digests, pos, _ = self.sweep()
+        d = digests.cpu().numpy()
+        return [(d[i].tobytes(), p) for i, p in enumerate(pos.tolist())]
+
     def _digest_tensor(self, keys):
         import torch
 
