@@ -16,8 +16,10 @@ from .engine import (  # noqa: F401
     HipVariableSha256HashEngine,
     SdfsConfig,
 )
+from .read import HipBufferReader, parse_map_slots  # noqa: F401
 
 __all__ = [
+    "HipBufferReader", "parse_map_slots",
     "Finger", "HashFunctionPool", "HipVariableMD5HashEngine", "HipVariableSha256HashEngine", "SdfsConfig",
     "SdfsCdcError", "POLY", "VARIABLE_MD5", "VARIABLE_SHA256", "VARIABLE_SHA256_160",
 ]

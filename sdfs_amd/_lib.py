@@ -18,7 +18,7 @@ TUNING_LIB = os.path.join(HERE, "libsdfs_cdc_tuning.so")
 LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
-                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h")]
+                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -76,6 +76,28 @@ class DevOut(ctypes.Structure):
         ("total", ctypes.c_void_p),
     ]
 
+
+class Pairs(ctypes.Structure):
+    """``sdfs_cdc_pairs`` (include/sdfs_read.h): device pointers of the parsed HashLocPairs."""
+
+    _fields_ = [
+        ("counts", ctypes.c_void_p),
+        ("hashes", ctypes.c_void_p),
+        ("hashloc", ctypes.c_void_p),
+        ("len", ctypes.c_void_p),
+        ("pos", ctypes.c_void_p),
+        ("offset", ctypes.c_void_p),
+        ("nlen", ctypes.c_void_p),
+        ("doop", ctypes.c_void_p),
+        ("flags", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("cap", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+READ_CORRUPT, READ_MISSING, READ_FETCH, READ_BOUNDS = 1, 2, 4, 8  # SDFS_CDC_READ_*
+READ_NONE = 0xFFFFFFFF
 
 # (name, restype, argtypes) for every entry point of include/sdfs_cdc.h
 _P = ctypes.POINTER
@@ -168,6 +190,17 @@ SIGNATURES = {
     "sdfs_cdc_aes_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _u64p]),
     "sdfs_cdc_aes_encrypt_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_int32,
                                                   _vp, _vp, _vp, _vp]),
+    # include/sdfs_read.h
+    "sdfs_cdc_map_pair_cap": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),
+    "sdfs_cdc_map_parse": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_uint32,
+                                          _P(Pairs), _vp]),
+    "sdfs_cdc_read_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(Pairs), ctypes.c_uint64, ctypes.c_uint64,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_read_chain_lens": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_read_assemble": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _P(Pairs), _vp, _vp,
+                                              _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_read_verify": (ctypes.c_int, [_vp, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                            _vp, ctypes.c_uint64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,703 @@
+// read_path.hip — write buffers rebuilt from their LongByteArrayMap slots on the device
+// (include/sdfs_read.h): the inverse of map_emit.hip plus the last hop.
+//
+// Reference: WritableCacheBuffer.initBuffer (WritableCacheBuffer.java:249-410) takes the buffer's
+// SparseDataChunk (SparseDataChunk.java:159-174, HashLocPair(byte[]) HashLocPair.java:86-97),
+// fetches the chunk of every pair before the first hashloc == 0 (HashBlobArchive.getChunk,
+// HashBlobArchive.java:1922-1944) and puts ck[offset .. offset + min(nlen, ck.length)) at pos into
+// a zeroed CHUNK_LENGTH array.  Here: one wave per buffer parses its image (map_parse_kernel),
+// one wave per buffer marks the directory entries it uses and a one-block scan ranks them
+// (read_plan), the caller runs the decryptor / decoder over the ranked list, one wave per buffer
+// settles its status and lays out per-pair {end, running max of end, source offset}
+// (assemble_status_kernel), and the gather kernel — the only pass over the data — writes every
+// output byte once.
+//
+// Gather: destination-driven.  A workgroup owns 64 KiB of one buffer's output, cut at absolute
+// 16-byte addresses; the buffer's pos / end / max-end / source arrays sit in LDS (<= kLdsPairs used pairs,
+// else they are searched in global memory).  A lane takes one 16-byte vector at a time: floor
+// entry by binary search (the previous vector's entry is tried first), and
+//   - the entry covers the whole vector and no later pair starts inside it: two aligned 16-byte
+//     loads of the source, realigned by a byte shift, one aligned 16-byte store;
+//   - nothing at or before the entry reaches the vector (max-end) and no pair starts inside: zeros;
+//   - else byte by byte: per byte the floor entry, then back to the last earlier pair that reaches
+//     the byte (the overlap rule; the walk ends where the running max of end stops reaching it).
+// The first and last vectors of a buffer whose ends are not 16-byte aligned are stored bytewise.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+
+#include "../../include/sdfs_read.h"
+#include "cdc_internal.h"
+
+namespace sdfs {
+namespace {
+
+constexpr uint32_t kNone = SDFS_CDC_READ_NONE;
+constexpr int kGatherThreads = 256;
+constexpr uint32_t kTileVecs = 4096;  // 16-byte vectors per workgroup (64 KiB): 4 groups of 4 per lane
+constexpr uint32_t kLdsPairs = 1024;  // used pairs per buffer staged in LDS (20 KiB)
+
+__device__ __forceinline__ uint32_t get_be32(const uint8_t* p) {
+    return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
+}
+
+__device__ __forceinline__ bool wave_any(bool v) { return __ballot(v) != 0; }
+
+// ---------------------------------------------------------------------------------------- parse
+
+struct ParseArgs {
+    const uint8_t* map;
+    uint32_t slot_bytes;
+    uint32_t hash_len;
+    sdfs_cdc_pairs p;
+    int32_t* tmp_pos;   // [nbuf*cap] scratch of the TreeMap path
+    uint32_t* tmp_dead; // [nbuf*cap]
+};
+
+// pair i of the image -> output slot `slot`
+__device__ __forceinline__ void put_pair(const ParseArgs& a, const uint8_t* rec, uint64_t slot) {
+    uint8_t* h = a.p.hashes + slot * 32;
+    for (uint32_t k = 0; k < a.hash_len; k++) h[k] = rec[k];
+    for (uint32_t k = a.hash_len; k < 32; k++) h[k] = 0;
+    const uint8_t* q = rec + a.hash_len;
+    a.p.hashloc[slot] = (uint64_t)get_be32(q) << 32 | get_be32(q + 4);
+    a.p.len[slot] = (int32_t)get_be32(q + 8);
+    a.p.pos[slot] = (int32_t)get_be32(q + 12);
+    a.p.offset[slot] = (int32_t)get_be32(q + 16);
+    a.p.nlen[slot] = (int32_t)get_be32(q + 20);
+}
+
+// one wave per buffer (every branch below is wave-uniform)
+__global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint8_t* img = a.map + (uint64_t)b * a.slot_bytes;
+    const uint32_t bal = a.hash_len + 24;
+    const int32_t zlen = (int32_t)get_be32(img + 5);
+    uint32_t status = 0, n = 0;
+    if (zlen > 0) {
+        if (13ull + (uint64_t)zlen * bal > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;  // BufferUnderflowException
+        else n = (uint32_t)zlen;
+    }
+    const uint8_t* recs = img + 9;
+    const uint32_t fo = a.hash_len + 8;  // the four ints of a pair: len, pos, offset, nlen
+    bool neg = false, unsorted = false;
+    for (uint32_t i = lane; i < n; i += 64) {
+        const uint8_t* q = recs + (uint64_t)i * bal + fo;
+        const int32_t ps = (int32_t)get_be32(q + 4);
+        neg |= ((int32_t)get_be32(q) | ps | (int32_t)get_be32(q + 8) | (int32_t)get_be32(q + 12)) < 0;
+        if (i > 0) unsorted |= (int32_t)get_be32(q + 4 - bal) >= ps;
+    }
+    if (wave_any(neg)) {  // HashLocPair.checkCorrupt
+        status = SDFS_CDC_READ_CORRUPT;
+        n = 0;
+    }
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    uint32_t count = n;
+    if (!wave_any(unsorted)) {
+        for (uint32_t i = lane; i < n; i += 64) put_pair(a, recs + (uint64_t)i * bal, base + i);
+    } else {
+        // TreeMap.put per pair in image order: a later pair with the same pos replaces the earlier
+        for (uint32_t i = lane; i < n; i += 64) a.tmp_pos[base + i] = (int32_t)get_be32(recs + (uint64_t)i * bal + fo + 4);
+        __syncthreads();
+        uint32_t live = 0;
+        for (uint32_t i = lane; i < n; i += 64) {
+            const int32_t ps = a.tmp_pos[base + i];
+            uint32_t dead = 0;
+            for (uint32_t j = i + 1; j < n; j++) dead |= a.tmp_pos[base + j] == ps;
+            a.tmp_dead[base + i] = dead;
+            live += !dead;
+        }
+        __syncthreads();
+        for (uint32_t i = lane; i < n; i += 64) {
+            if (a.tmp_dead[base + i]) continue;
+            const int32_t ps = a.tmp_pos[base + i];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < n; j++) rank += !a.tmp_dead[base + j] && a.tmp_pos[base + j] < ps;
+            put_pair(a, recs + (uint64_t)i * bal, base + rank);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o);
+        count = live;
+    }
+    if (lane == 0) {
+        a.p.counts[b] = count;
+        a.p.flags[b] = img[0];
+        a.p.doop[b] = status ? 0 : get_be32(recs + (uint64_t)n * bal);
+        a.p.status[b] = status;
+    }
+}
+
+// ----------------------------------------------------------------------------------------- plan
+
+struct PlanArgs {
+    sdfs_cdc_pairs p;
+    uint64_t pos_base;
+    uint64_t n_store;
+    const uint64_t* store_off;
+    const uint32_t* store_len;
+    const uint32_t* store_raw;
+    uint32_t* pair_fetch;
+    uint32_t* fetch_count;
+    uint64_t* src_off;
+    uint32_t* src_len;
+    uint64_t* dst_off;
+    uint32_t* dst_cap;
+    uint64_t* plain_off;
+    uint64_t* total_bytes;
+    uint32_t* mark;  // [n_store] 1 = needed, then its fetch index
+};
+
+// one wave per buffer: the terminator rule, MISSING, and the directory entries it needs
+__global__ __launch_bounds__(64) void plan_mark_kernel(PlanArgs a) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    const uint32_t st = a.p.status[b];
+    const uint32_t n = st ? 0 : min(a.p.counts[b], a.p.cap);
+    uint32_t used = n;
+    for (uint32_t i = lane; i < n; i += 64)
+        if (a.p.hashloc[base + i] == 0) used = min(used, i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) used = min(used, (uint32_t)__shfl_xor(used, o));
+    bool missing = false;
+    for (uint32_t i = lane; i < used; i += 64) {
+        const uint64_t hl = a.p.hashloc[base + i];
+        missing |= hl < a.pos_base || hl - a.pos_base >= a.n_store;
+    }
+    if (wave_any(missing)) {
+        used = 0;
+        if (lane == 0) a.p.status[b] = st | SDFS_CDC_READ_MISSING;
+    }
+    for (uint32_t i = lane; i < a.p.cap; i += 64) {
+        uint32_t f = kNone;
+        if (i < used) {
+            f = (uint32_t)(a.p.hashloc[base + i] - a.pos_base);
+            a.mark[f] = 1;
+        }
+        a.pair_fetch[base + i] = f;
+    }
+}
+
+// one block: rank the marked directory entries and lay out their fetches.  The directory is
+// walked in tiles of 1024 entries (coalesced), each tile scanned wave by wave, the running totals
+// carried from tile to tile.
+__global__ __launch_bounds__(1024) void plan_scan_kernel(PlanArgs a) {
+    __shared__ uint32_t wc[16];
+    __shared__ uint64_t wd[16], wp[16];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t cf = 0;          // fetches before this tile
+    uint64_t cd = 0, cp = 0;  // their chunk-area / decrypted-area bytes
+    for (uint64_t k0 = 0; k0 < a.n_store; k0 += 1024) {
+        const uint64_t k = k0 + t;
+        const bool on = k < a.n_store && a.mark[k] != 0;
+        const uint32_t raw = on ? a.store_raw[k] : 0, sl = on ? a.store_len[k] : 0;
+        const uint64_t d = on ? ((uint64_t)raw + 15) & ~15ull : 0, p = on ? ((uint64_t)sl + 15) & ~15ull : 0;
+        uint32_t ic = on;  // inclusive scans over the wave
+        uint64_t id = d, ip = p;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t vc = __shfl_up(ic, o);
+            const unsigned long long vd = __shfl_up((unsigned long long)id, o), vp = __shfl_up((unsigned long long)ip, o);
+            if (lane >= (uint32_t)o) {
+                ic += vc;
+                id += vd;
+                ip += vp;
+            }
+        }
+        if (lane == 63) {
+            wc[wave] = ic;
+            wd[wave] = id;
+            wp[wave] = ip;
+        }
+        __syncthreads();
+        uint32_t bc = cf, tc = 0;
+        uint64_t bd = cd, bp = cp, td = 0, tp = 0;
+        for (uint32_t w = 0; w < 16; w++) {
+            if (w < wave) {
+                bc += wc[w];
+                bd += wd[w];
+                bp += wp[w];
+            }
+            tc += wc[w];
+            td += wd[w];
+            tp += wp[w];
+        }
+        if (on) {
+            const uint32_t f = bc + ic - 1;
+            a.src_off[f] = a.store_off[k];
+            a.src_len[f] = sl;
+            a.dst_off[f] = bd + id - d;
+            a.dst_cap[f] = raw;
+            if (a.plain_off) a.plain_off[f] = bp + ip - p;
+            a.mark[k] = f;
+        }
+        cf += tc;
+        cd += td;
+        cp += tp;
+        __syncthreads();  // the wave totals are rewritten by the next tile
+    }
+    if (t == 0) {
+        *a.fetch_count = cf;
+        a.total_bytes[0] = cd;
+        a.total_bytes[1] = cp;
+    }
+}
+
+__global__ __launch_bounds__(256) void plan_remap_kernel(uint32_t* pair_fetch, uint64_t n, const uint32_t* mark) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = pair_fetch[i];
+    if (k != kNone) pair_fetch[i] = mark[k];
+}
+
+__global__ __launch_bounds__(256) void chain_lens_kernel(const uint32_t* in, const uint32_t* count, uint64_t n_max,
+                                                         uint32_t* out) {
+    const uint64_t n = count ? min<uint64_t>(*count, n_max) : n_max;
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = in[i] == UINT32_MAX ? 0 : in[i];
+}
+
+// ------------------------------------------------------------------------------------- assemble
+
+struct AsmArgs {
+    sdfs_cdc_pairs p;
+    uint32_t nbuf;
+    uint32_t chunk_length;
+    const uint32_t* pair_fetch;
+    const uint8_t* chunks;
+    const uint64_t* fetch_off;
+    const uint32_t* fetch_len;
+    uint8_t* out;
+    uint32_t* nused;   // [nbuf] pairs the gather places (0 for a failed buffer)
+    int32_t* end;      // [nbuf*cap] pos + c
+    int32_t* maxend;   // [nbuf*cap] max of end[0..i]
+    uint64_t* src;     // [nbuf*cap] offset in chunks of the byte that goes to pos
+    uint32_t tiles_per_buf;
+};
+
+// one wave per buffer: FETCH / BOUNDS, then the gather's per-pair arrays
+__global__ __launch_bounds__(64) void assemble_status_kernel(AsmArgs a) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    uint32_t st = a.p.status[b];
+    const uint32_t n = st ? 0 : min(a.p.counts[b], a.p.cap);
+    uint32_t used = n;  // used pairs are a prefix (the terminator rule)
+    for (uint32_t i = lane; i < n; i += 64)
+        if (a.pair_fetch[base + i] == kNone) used = min(used, i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) used = min(used, (uint32_t)__shfl_xor(used, o));
+    bool failed = false;
+    for (uint32_t i = lane; i < used; i += 64) failed |= a.fetch_len[a.pair_fetch[base + i]] == UINT32_MAX;
+    if (wave_any(failed)) {
+        st |= SDFS_CDC_READ_FETCH;
+    } else {
+        bool oob = false;
+        for (uint32_t i = lane; i < used; i += 64) {
+            const int64_t ck = a.fetch_len[a.pair_fetch[base + i]];
+            const int64_t nlen = a.p.nlen[base + i], pos = a.p.pos[base + i], off = a.p.offset[base + i];
+            const int64_t c = nlen > ck ? ck : nlen;
+            oob |= pos > (int64_t)a.chunk_length || pos + c > (int64_t)a.chunk_length || off + c > ck;
+        }
+        if (wave_any(oob)) st |= SDFS_CDC_READ_BOUNDS;
+    }
+    if (st) used = 0;
+    if (lane == 0) {
+        a.p.status[b] = st;
+        a.nused[b] = used;
+    }
+    int32_t carry = INT_MIN;
+    for (uint32_t i0 = 0; i0 < used; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        int32_t e = INT_MIN;
+        if (i < used) {
+            const uint32_t f = a.pair_fetch[base + i];
+            const int64_t ck = a.fetch_len[f];
+            const int64_t nlen = a.p.nlen[base + i];
+            const int64_t c = nlen > ck ? ck : nlen;
+            e = (int32_t)(a.p.pos[base + i] + c);  // <= chunk_length <= INT32_MAX
+            a.end[base + i] = e;
+            a.src[base + i] = a.fetch_off[f] + (uint64_t)a.p.offset[base + i];
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t v = __shfl_up(e, o);
+            if (lane >= (uint32_t)o) e = max(e, v);
+        }
+        e = max(e, carry);
+        if (i < used) a.maxend[base + i] = e;
+        carry = __shfl(e, 63);
+    }
+}
+
+// view of one buffer's placed pairs (LDS or global)
+struct PairView {
+    const int32_t* pos;
+    const int32_t* end;
+    const int32_t* maxend;
+    const uint64_t* src;
+    int32_t n;
+};
+
+// largest k with pos[k] <= x, -1 if none; `hint` = the answer for a nearby x
+__device__ __forceinline__ int32_t floor_pair(const PairView& v, int32_t x, int32_t hint) {
+    if (hint >= -1 && hint < v.n && (hint < 0 || v.pos[hint] <= x) && (hint + 1 >= v.n || v.pos[hint + 1] > x))
+        return hint;
+    int32_t lo = 0, hi = v.n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (v.pos[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo - 1;
+}
+
+// byte x of the buffer; k = floor entry of some x' <= x
+__device__ __forceinline__ uint8_t gather_byte(const PairView& v, const uint8_t* chunks, int32_t x, int32_t& k) {
+    while (k + 1 < v.n && v.pos[k + 1] <= x) k++;
+    for (int32_t j = k; j >= 0 && v.maxend[j] > x; j--)  // the last pair in pos order that covers x
+        if (v.end[j] > x) return chunks[v.src[j] + (uint64_t)(x - v.pos[j])];
+    return 0;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
+    __shared__ int32_t s_pos[LDS ? kLdsPairs : 1], s_end[LDS ? kLdsPairs : 1], s_max[LDS ? kLdsPairs : 1];
+    __shared__ uint64_t s_src[LDS ? kLdsPairs : 1];
+    const uint32_t b = blockIdx.x / a.tiles_per_buf;
+    const uint32_t tile = blockIdx.x % a.tiles_per_buf;
+    const uint32_t tid = threadIdx.x;
+    const int64_t cl = a.chunk_length;
+    uint8_t* ob = a.out + (uint64_t)b * a.chunk_length;
+    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(ob) & 15);
+    const uint64_t nvec = ((uint64_t)head + a.chunk_length + 15) / 16;  // vectors at absolute 16-byte addresses
+    const uint64_t v0 = (uint64_t)tile * kTileVecs;
+    if (v0 >= nvec) return;  // uniform over the workgroup
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    PairView pv{a.p.pos + base, a.end + base, a.maxend + base, a.src + base, (int32_t)a.nused[b]};
+    if (LDS) {
+        if (pv.n > (int32_t)kLdsPairs) pv.n = 0;  // not reached: the host picks the global form above kLdsPairs
+        for (int32_t i = tid; i < pv.n; i += kGatherThreads) {
+            s_pos[i] = pv.pos[i];
+            s_end[i] = pv.end[i];
+            s_max[i] = pv.maxend[i];
+            s_src[i] = pv.src[i];
+        }
+        __syncthreads();
+        pv.pos = s_pos;
+        pv.end = s_end;
+        pv.maxend = s_max;
+        pv.src = s_src;
+    }
+    // per group of kIt vectors a lane makes three passes, so that the source loads of all of them
+    // are in flight together: classify, load, realign + store
+    constexpr int kIt = 4;
+    enum : uint32_t { kSkip, kCopy, kZero, kBytes, kEdge };
+    int32_t k = -2;
+#pragma unroll 1
+    for (uint64_t g0 = v0; g0 < min(v0 + kTileVecs, nvec); g0 += kIt * kGatherThreads) {
+    const uint64_t w0 = g0 + tid;  // the lane's vectors: w0 + it * kGatherThreads
+    uint32_t mode[kIt];
+    int32_t kf[kIt];
+    uintptr_t sa[kIt];
+#pragma unroll
+    for (int it = 0; it < kIt; it++) {
+        mode[it] = kSkip;
+        kf[it] = -1;
+        sa[it] = 0;
+        const uint64_t v = w0 + (uint64_t)it * kGatherThreads;
+        if (v >= nvec) continue;
+        const int64_t o = (int64_t)v * 16 - head;  // buffer offset of the vector's first byte
+        const int32_t x0 = (int32_t)max<int64_t>(o, 0);
+        k = floor_pair(pv, x0, k);
+        kf[it] = k;
+        if (o < 0 || o + 16 > cl) {  // a buffer end that is not 16-byte aligned
+            mode[it] = kEdge;
+            continue;
+        }
+        const int64_t next = k + 1 < pv.n ? pv.pos[k + 1] : INT64_MAX;
+        if (next >= o + 16 && k >= 0 && pv.end[k] >= o + 16) {
+            mode[it] = kCopy;
+            sa[it] = reinterpret_cast<uintptr_t>(a.chunks + pv.src[k] + (uint64_t)(x0 - pv.pos[k]));
+        } else if (next >= o + 16 && (k < 0 || pv.maxend[k] <= o)) {
+            mode[it] = kZero;
+        } else {
+            mode[it] = kBytes;
+        }
+    }
+    uint4 lo[kIt], hi[kIt];
+#pragma unroll
+    for (int it = 0; it < kIt; it++) {
+        lo[it] = hi[it] = make_uint4(0, 0, 0, 0);
+        if (mode[it] != kCopy) continue;
+        const uint32_t sh = (uint32_t)(sa[it] & 15);
+        const uint4* ap = reinterpret_cast<const uint4*>(sa[it] - sh);
+        lo[it] = ap[0];
+        if (sh) hi[it] = ap[1];  // holds bytes the vector needs: inside the chunk area
+    }
+#pragma unroll
+    for (int it = 0; it < kIt; it++) {
+        if (mode[it] == kSkip) continue;
+        const uint64_t v = w0 + (uint64_t)it * kGatherThreads;
+        const int64_t o = (int64_t)v * 16 - head;
+        uint8_t* dst = ob + o;
+        int32_t kk = kf[it];
+        if (mode[it] == kEdge) {
+            for (int j = 0; j < 16; j++) {
+                const int64_t x = o + j;
+                if (x >= 0 && x < cl) dst[j] = gather_byte(pv, a.chunks, (int32_t)x, kk);
+            }
+            continue;
+        }
+        uint4 w = make_uint4(0, 0, 0, 0);
+        if (mode[it] == kCopy) {
+            const uint32_t sh = (uint32_t)(sa[it] & 15), q = sh >> 2, r = sh & 3;
+            const uint4 l = lo[it], h = hi[it];
+            uint32_t t0, t1, t2, t3, t4;
+            if (q == 0) { t0 = l.x; t1 = l.y; t2 = l.z; t3 = l.w; t4 = h.x; }
+            else if (q == 1) { t0 = l.y; t1 = l.z; t2 = l.w; t3 = h.x; t4 = h.y; }
+            else if (q == 2) { t0 = l.z; t1 = l.w; t2 = h.x; t3 = h.y; t4 = h.z; }
+            else { t0 = l.w; t1 = h.x; t2 = h.y; t3 = h.z; t4 = h.w; }
+            w.x = __builtin_amdgcn_alignbyte(t1, t0, r);
+            w.y = __builtin_amdgcn_alignbyte(t2, t1, r);
+            w.z = __builtin_amdgcn_alignbyte(t3, t2, r);
+            w.w = __builtin_amdgcn_alignbyte(t4, t3, r);
+        } else if (mode[it] == kBytes) {
+            uint32_t ws[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                uint32_t word = 0;
+#pragma unroll
+                for (int bb = 0; bb < 4; bb++)
+                    word |= (uint32_t)gather_byte(pv, a.chunks, (int32_t)o + 4 * j + bb, kk) << (8 * bb);
+                ws[j] = word;
+            }
+            w = make_uint4(ws[0], ws[1], ws[2], ws[3]);
+        }
+        *reinterpret_cast<uint4*>(dst) = w;
+    }
+    }
+}
+
+// --------------------------------------------------------------------------------------- verify
+
+struct VerifyArgs {
+    sdfs_cdc_pairs p;
+    uint32_t hash_len;
+    const uint32_t* pair_fetch;
+    const uint32_t* fetch_len;
+    const uint8_t* digests;  // [fetch*32]
+    uint8_t* pair_bad;
+    uint32_t* bad_count;
+};
+
+__global__ __launch_bounds__(64) void verify_compare_kernel(VerifyArgs a) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    uint32_t nbad = 0;
+    for (uint32_t i = lane; i < a.p.cap; i += 64) {
+        const uint32_t f = a.pair_fetch[base + i];
+        uint32_t bad = 0;
+        if (f != kNone && a.fetch_len[f] != UINT32_MAX) {
+            const uint8_t* h = a.p.hashes + (base + i) * 32;
+            const uint8_t* d = a.digests + (uint64_t)f * 32;
+            for (uint32_t k = 0; k < a.hash_len; k++) bad |= h[k] != d[k];
+        }
+        a.pair_bad[base + i] = (uint8_t)bad;
+        nbad += bad;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nbad += __shfl_xor(nbad, o);
+    if (lane == 0) a.bad_count[b] = nbad;
+}
+
+// ----------------------------------------------------------------------------------------- host
+
+bool pairs_complete(const sdfs_cdc_pairs* p) {
+    return p && p->counts && p->hashes && p->hashloc && p->len && p->pos && p->offset && p->nlen && p->doop &&
+           p->flags && p->status && p->cap;
+}
+
+// per-call scratch in stream order; released in the destructor (the frees are enqueued behind
+// whatever was launched on the stream before it runs)
+struct Scratch {
+    hipStream_t s;
+    void* ptrs[6] = {};
+    int n = 0;
+    explicit Scratch(hipStream_t st) : s(st) {}
+    template <typename T>
+    hipError_t get(T** out, size_t count) {
+        void* p = nullptr;
+        const hipError_t e = hipMallocAsync(&p, std::max<size_t>(count, 1) * sizeof(T), s);
+        if (e == hipSuccess) ptrs[n++] = p;
+        *out = static_cast<T*>(p);
+        return e;
+    }
+    ~Scratch() {
+        for (int i = 0; i < n; i++) (void)hipFreeAsync(ptrs[i], s);
+    }
+};
+
+#define RD_TRY(expr)                                                                               \
+    do {                                                                                           \
+        const hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess)                                                                      \
+            return fail_status(e_ == hipErrorOutOfMemory ? SDFS_CDC_ENOMEM : SDFS_CDC_EHIP, "%s: %s", #expr, \
+                               hipGetErrorString(e_));                                             \
+    } while (0)
+
+int set_device(int device) {
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) return fail_status(SDFS_CDC_ENODEV, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
+    return SDFS_CDC_OK;
+}
+
+}  // namespace
+}  // namespace sdfs
+
+using namespace sdfs;
+
+extern "C" {
+
+uint32_t sdfs_cdc_map_pair_cap(uint32_t slot_bytes, uint32_t hash_len) {
+    return slot_bytes < 13 ? 0 : (slot_bytes - 13) / (hash_len + 24);
+}
+
+int sdfs_cdc_map_parse(int device, uint32_t nbuf, const uint8_t* d_map, uint32_t slot_bytes, uint32_t hash_len,
+                       const sdfs_cdc_pairs* pairs, void* stream) {
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (hash_len != 32 && hash_len != 16)
+        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: HashLocPair holds 32 (SHA-256) or 16 (MD5) bytes", hash_len);
+    if (slot_bytes < 13) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
+    if (pairs->cap < sdfs_cdc_map_pair_cap(slot_bytes, hash_len))
+        return fail_status(SDFS_CDC_ECAP, "pairs.cap %u < %u pairs a %u-byte slot can hold", pairs->cap,
+                           sdfs_cdc_map_pair_cap(slot_bytes, hash_len), slot_bytes);
+    if (nbuf && !d_map) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (nbuf == 0) return SDFS_CDC_OK;
+    if (const int rc = set_device(device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc(s);
+    ParseArgs a{d_map, slot_bytes, hash_len, *pairs, nullptr, nullptr};
+    RD_TRY(sc.get(&a.tmp_pos, (size_t)nbuf * pairs->cap));
+    RD_TRY(sc.get(&a.tmp_dead, (size_t)nbuf * pairs->cap));
+    hipLaunchKernelGGL(map_parse_kernel, dim3(nbuf), dim3(64), 0, s, a);
+    RD_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_plan(int device, uint32_t nbuf, const sdfs_cdc_pairs* pairs, uint64_t pos_base, uint64_t n_store,
+                       const uint64_t* d_store_off, const uint32_t* d_store_len, const uint32_t* d_store_raw_len,
+                       uint32_t* d_pair_fetch, uint32_t* d_fetch_count, uint64_t* d_src_off, uint32_t* d_src_len,
+                       uint64_t* d_dst_off, uint32_t* d_dst_cap, uint64_t* d_plain_off, uint64_t* d_total_bytes,
+                       void* stream) {
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (!d_fetch_count || !d_total_bytes || (nbuf && !d_pair_fetch)) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_store && (!d_store_off || !d_store_len || !d_store_raw_len || !d_src_off || !d_src_len || !d_dst_off ||
+                    !d_dst_cap))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_store >= UINT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n_store %llu: fetch indices are 32-bit",
+                                                  (unsigned long long)n_store);
+    if (const int rc = set_device(device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc(s);
+    PlanArgs a{*pairs,    pos_base,  n_store,   d_store_off, d_store_len, d_store_raw_len, d_pair_fetch, d_fetch_count,
+               d_src_off, d_src_len, d_dst_off, d_dst_cap,   d_plain_off, d_total_bytes,   nullptr};
+    RD_TRY(sc.get(&a.mark, (size_t)n_store));
+    RD_TRY(hipMemsetAsync(a.mark, 0, std::max<size_t>(n_store, 1) * 4, s));
+    if (nbuf) hipLaunchKernelGGL(plan_mark_kernel, dim3(nbuf), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+    const uint64_t slots = (uint64_t)nbuf * pairs->cap;
+    if (slots)
+        hipLaunchKernelGGL(plan_remap_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, d_pair_fetch, slots,
+                           a.mark);
+    RD_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_chain_lens(int device, const uint32_t* d_in_len, const uint32_t* d_count, uint64_t n_max,
+                             uint32_t* d_out_len, void* stream) {
+    if (n_max && (!d_in_len || !d_out_len)) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_max >= (1ull << 39)) return fail_status(SDFS_CDC_EINVAL, "n_max %llu too large", (unsigned long long)n_max);
+    if (n_max == 0) return SDFS_CDC_OK;
+    if (const int rc = set_device(device)) return rc;
+    hipLaunchKernelGGL(chain_lens_kernel, dim3((uint32_t)((n_max + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), d_in_len, d_count, n_max, d_out_len);
+    RD_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_assemble(int device, uint32_t nbuf, uint32_t chunk_length, const sdfs_cdc_pairs* pairs,
+                           const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
+                           const uint32_t* d_fetch_len, uint8_t* d_out, void* stream) {
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (chunk_length < 1 || chunk_length > (uint32_t)INT32_MAX)
+        return fail_status(SDFS_CDC_EINVAL, "chunk_length %u: 1 .. 2^31 - 1 (HashLocPair.pos is an int)", chunk_length);
+    if (nbuf && (!d_pair_fetch || !d_chunks || !d_fetch_off || !d_fetch_len || !d_out))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (nbuf == 0) return SDFS_CDC_OK;
+    const uint32_t tiles = (uint32_t)(((uint64_t)chunk_length + 30) / 16 / kTileVecs + 1);
+    if ((uint64_t)tiles * nbuf > (uint64_t)INT32_MAX)
+        return fail_status(SDFS_CDC_EINVAL, "%u buffers of %u bytes: split the batch", nbuf, chunk_length);
+    if (const int rc = set_device(device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc(s);
+    AsmArgs a{*pairs, nbuf, chunk_length, d_pair_fetch, d_chunks, d_fetch_off, d_fetch_len, d_out,
+              nullptr, nullptr, nullptr, nullptr, tiles};
+    const size_t slots = (size_t)nbuf * pairs->cap;
+    RD_TRY(sc.get(&a.nused, nbuf));
+    RD_TRY(sc.get(&a.end, slots));
+    RD_TRY(sc.get(&a.maxend, slots));
+    RD_TRY(sc.get(&a.src, slots));
+    hipLaunchKernelGGL(assemble_status_kernel, dim3(nbuf), dim3(64), 0, s, a);
+    const dim3 grid((uint32_t)((uint64_t)tiles * nbuf));
+    if (pairs->cap <= kLdsPairs) hipLaunchKernelGGL(gather_kernel<true>, grid, dim3(kGatherThreads), 0, s, a);
+    else hipLaunchKernelGGL(gather_kernel<false>, grid, dim3(kGatherThreads), 0, s, a);
+    RD_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_verify(sdfs_cdc_engine* engine, uint32_t nbuf, const sdfs_cdc_pairs* pairs, uint32_t hash_len,
+                         const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
+                         const uint32_t* d_fetch_len, const uint32_t* d_fetch_count, uint64_t n_fetch_max,
+                         uint8_t* d_pair_bad, uint32_t* d_bad_count, void* stream) {
+    if (!engine) return fail_status(SDFS_CDC_EINVAL, "null engine");
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (hash_len != 32 && hash_len != 16)
+        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: HashLocPair holds 32 (SHA-256) or 16 (MD5) bytes", hash_len);
+    if (nbuf && (!d_pair_fetch || !d_pair_bad || !d_bad_count)) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if ((nbuf || n_fetch_max) && (!d_chunks || !d_fetch_off || !d_fetch_len))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_fetch_max >= (1ull << 39))
+        return fail_status(SDFS_CDC_EINVAL, "n_fetch_max %llu too large", (unsigned long long)n_fetch_max);
+    const int dl = sdfs_cdc_digest_len(engine);
+    if (dl < 0) return fail_status(SDFS_CDC_EINVAL, "not a live engine handle");
+    if ((uint32_t)dl != hash_len)
+        return fail_status(SDFS_CDC_EINVAL, "engine digests are %d bytes, the pairs hold %u", dl, hash_len);
+    if (nbuf == 0) return SDFS_CDC_OK;
+    hipPointerAttribute_t at;
+    RD_TRY(hipPointerGetAttributes(&at, d_pair_bad));
+    if (const int rc = set_device(at.device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc(s);
+    uint32_t* lens = nullptr;
+    uint8_t* digests = nullptr;
+    RD_TRY(sc.get(&lens, (size_t)n_fetch_max));
+    RD_TRY(sc.get(&digests, (size_t)n_fetch_max * 32));
+    if (n_fetch_max) {
+        hipLaunchKernelGGL(chain_lens_kernel, dim3((uint32_t)((n_fetch_max + 255) / 256)), dim3(256), 0, s, d_fetch_len,
+                           d_fetch_count, n_fetch_max, lens);
+        RD_TRY(hipGetLastError());
+        const int rc = sdfs_cdc_hash_device(engine, d_chunks, d_fetch_off, lens, d_fetch_count, n_fetch_max, digests, stream);
+        if (rc) return rc;
+    }
+    VerifyArgs a{*pairs, hash_len, d_pair_fetch, d_fetch_len, digests, d_pair_bad, d_bad_count};
+    hipLaunchKernelGGL(verify_compare_kernel, dim3(nbuf), dim3(64), 0, s, a);
+    RD_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+}  // extern "C"

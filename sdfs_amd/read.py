@@ -1,0 +1,236 @@
+"""Read path on the MI355X (include/sdfs_read.h): write buffers rebuilt from their map slots.
+
+The way back of :mod:`sdfs_amd.meta`: ``WritableCacheBuffer.initBuffer``
+(WritableCacheBuffer.java:249-410) parses the buffer's ``SparseDataChunk``
+(SparseDataChunk.java:159-174), fetches the chunk of every ``HashLocPair`` before the first
+``hashloc == 0`` (``HashBlobArchive.getChunk``, HashBlobArchive.java:1922-1944: decrypt, read nz,
+LZ4-decode, optionally re-hash) and puts ``ck[offset : offset + min(nlen, len(ck))]`` at ``pos``
+into a zeroed CHUNK_LENGTH array.
+
+* :func:`parse_map_slots` — the slots' images as a :class:`ParsedPairs` (device tensors).
+* :class:`HipBufferReader` — the whole path for a batch of buffers: parse -> plan -> (decrypt ->
+  chain_lens) -> framed decode -> assemble -> (verify).
+
+PyTorch allocates HBM and hands over the stream; every step runs the library's HIP kernels.
+No CPU fallback: a failure raises :class:`SdfsCdcError`.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+
+from . import _lib
+from ._lib import READ_BOUNDS, READ_CORRUPT, READ_FETCH, READ_MISSING, READ_NONE, check  # noqa: F401
+
+
+def pair_cap(slot_len: int, hash_len: int = 32) -> int:
+    """Pairs a slot can hold: (slot_len - 13) // (hash_len + 24)."""
+    return int(_lib.load().sdfs_cdc_map_pair_cap(int(slot_len), int(hash_len)))
+
+
+@dataclass
+class ParsedPairs:
+    """``sdfs_cdc_pairs``: buffer b's pair i at row b, column i (i < counts[b]), ascending pos."""
+
+    nbuf: int
+    cap: int
+    hash_len: int
+    counts: object   # int32 [nbuf]
+    hashes: object   # uint8 [nbuf, cap, 32]
+    hashloc: object  # int64 [nbuf, cap]
+    len: object      # int32 [nbuf, cap]
+    pos: object
+    offset: object
+    nlen: object
+    doop: object     # int32 [nbuf]
+    flags: object    # uint8 [nbuf]
+    status: object   # int32 [nbuf], SDFS_CDC_READ_* bits
+
+    def __post_init__(self):
+        self.c = _lib.Pairs(
+            counts=self.counts.data_ptr(), hashes=self.hashes.data_ptr(), hashloc=self.hashloc.data_ptr(),
+            len=self.len.data_ptr(), pos=self.pos.data_ptr(), offset=self.offset.data_ptr(),
+            nlen=self.nlen.data_ptr(), doop=self.doop.data_ptr(), flags=self.flags.data_ptr(),
+            status=self.status.data_ptr(), cap=self.cap, reserved=0)
+
+
+def _stream(t, stream):
+    import torch
+
+    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+
+
+def parse_map_slots(m, nbuf: int, slot_len: int, hash_len: int = 32, device: int = 0, stream=None) -> ParsedPairs:
+    """m: device uint8 tensor holding nbuf slots of slot_len bytes (``emit_map_slots``' output)."""
+    import torch
+
+    cap = max(pair_cap(slot_len, hash_len), 1)
+    dev = m.device
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
+    pairs = ParsedPairs(nbuf, cap, hash_len, z(max(nbuf, 1), torch.int32), z((max(nbuf, 1), cap, 32), torch.uint8),
+                        z((max(nbuf, 1), cap), torch.int64), z((max(nbuf, 1), cap), torch.int32),
+                        z((max(nbuf, 1), cap), torch.int32), z((max(nbuf, 1), cap), torch.int32),
+                        z((max(nbuf, 1), cap), torch.int32), z(max(nbuf, 1), torch.int32),
+                        z(max(nbuf, 1), torch.uint8), z(max(nbuf, 1), torch.int32))
+    if m.numel() < nbuf * slot_len:
+        raise ValueError(f"map holds {m.numel()} bytes, {nbuf} slots of {slot_len} need {nbuf * slot_len}")
+    check(_lib.load().sdfs_cdc_map_parse(int(device), int(nbuf), m.data_ptr(), int(slot_len), int(hash_len),
+                                         ctypes.byref(pairs.c), _stream(m, stream)))
+    return pairs
+
+
+def plan_reads(pairs: ParsedPairs, store_off, store_len, store_raw_len, pos_base: int, device: int = 0, stream=None):
+    """``sdfs_cdc_read_plan``.  Directory tensors: store_off i64[n], store_len / store_raw_len i32[n].
+    Returns a dict of device tensors: pair_fetch i32[nbuf, cap] (-1 = not used), fetch_count i32[1],
+    src_off, src_len, dst_off, dst_cap, plain_off (n entries each, fetch_count valid), total_bytes
+    i64[2] (chunk area, decrypted-record area)."""
+    import torch
+
+    n = int(store_len.shape[0])
+    dev = pairs.counts.device
+    e = lambda dt: torch.empty(max(n, 1), dtype=dt, device=dev)  # noqa: E731
+    out = dict(pair_fetch=torch.empty((max(pairs.nbuf, 1), pairs.cap), dtype=torch.int32, device=dev),
+               fetch_count=torch.zeros(1, dtype=torch.int32, device=dev), src_off=e(torch.int64),
+               src_len=e(torch.int32), dst_off=e(torch.int64), dst_cap=e(torch.int32), plain_off=e(torch.int64),
+               total_bytes=torch.zeros(2, dtype=torch.int64, device=dev))
+    check(_lib.load().sdfs_cdc_read_plan(
+        int(device), pairs.nbuf, ctypes.byref(pairs.c), int(pos_base), n, store_off.data_ptr() if n else None,
+        store_len.data_ptr() if n else None, store_raw_len.data_ptr() if n else None, out["pair_fetch"].data_ptr(),
+        out["fetch_count"].data_ptr(), out["src_off"].data_ptr(), out["src_len"].data_ptr(),
+        out["dst_off"].data_ptr(), out["dst_cap"].data_ptr(), out["plain_off"].data_ptr(),
+        out["total_bytes"].data_ptr(), _stream(pairs.counts, stream)))
+    return out
+
+
+def chain_lens(in_len, count=None, device: int = 0, stream=None):
+    """``sdfs_cdc_read_chain_lens``: the decryptor's output lengths as decoder input lengths."""
+    import torch
+
+    out = torch.empty_like(in_len)
+    check(_lib.load().sdfs_cdc_read_chain_lens(int(device), in_len.data_ptr(),
+                                               count.data_ptr() if count is not None else None,
+                                               int(in_len.shape[0]), out.data_ptr(), _stream(in_len, stream)))
+    return out
+
+
+def assemble(pairs: ParsedPairs, chunk_length: int, pair_fetch, chunks, fetch_off, fetch_len, out=None,
+             device: int = 0, stream=None):
+    """``sdfs_cdc_read_assemble``: settles pairs.status and writes the buffers (uint8 [nbuf, chunk_length])."""
+    import torch
+
+    if out is None:
+        out = torch.empty((pairs.nbuf, chunk_length), dtype=torch.uint8, device=chunks.device)
+    check(_lib.load().sdfs_cdc_read_assemble(int(device), pairs.nbuf, int(chunk_length), ctypes.byref(pairs.c),
+                                             pair_fetch.data_ptr(), chunks.data_ptr(), fetch_off.data_ptr(),
+                                             fetch_len.data_ptr(), out.data_ptr(), _stream(chunks, stream)))
+    return out
+
+
+def verify_reads(engine, pairs: ParsedPairs, pair_fetch, chunks, fetch_off, fetch_len, fetch_count, stream=None):
+    """``sdfs_cdc_read_verify``: (pair_bad uint8 [nbuf, cap], bad_count int32 [nbuf])."""
+    import torch
+
+    dev = chunks.device
+    bad = torch.empty((max(pairs.nbuf, 1), pairs.cap), dtype=torch.uint8, device=dev)
+    cnt = torch.empty(max(pairs.nbuf, 1), dtype=torch.int32, device=dev)
+    check(_lib.load().sdfs_cdc_read_verify(engine._h, pairs.nbuf, ctypes.byref(pairs.c), pairs.hash_len,
+                                           pair_fetch.data_ptr(), chunks.data_ptr(), fetch_off.data_ptr(),
+                                           fetch_len.data_ptr(), fetch_count.data_ptr(), int(fetch_len.shape[0]),
+                                           bad.data_ptr(), cnt.data_ptr(), _stream(chunks, stream)))
+    return bad, cnt
+
+
+@dataclass
+class ReadInfo:
+    fetch_count: int        # distinct stored records the batch needed
+    pairs: ParsedPairs
+    pair_fetch: object      # int32 [nbuf, cap], -1 = not used
+    bad_count: object = None  # verify: int32 [nbuf] pairs whose hash differs from their chunk's digest
+    pair_bad: object = None   # verify: uint8 [nbuf, cap]
+
+
+class HipBufferReader:
+    """WritableCacheBuffer.initBuffer for batches of buffers on one GPU.
+
+    aes: a :class:`sdfs_amd.aes.HipEncryptUtils` (or the key bytes) when the store is encrypted, with
+    iv the archive's 16 bytes.  engine: the hash engine, needed for ``verify=True``."""
+
+    def __init__(self, chunk_length: int, hash_len: int = 32, device: int = 0, aes=None, iv=None, engine=None):
+        from .lz4 import HipLz4Compressor
+
+        self.chunk_length = int(chunk_length)
+        self.hash_len = int(hash_len)
+        self.device = int(device)
+        self.engine = engine
+        self._own_aes = False
+        if aes is not None and not hasattr(aes, "decrypt_device"):
+            from .aes import HipEncryptUtils
+
+            aes = HipEncryptUtils(bytes(aes), device)
+            self._own_aes = True
+        if aes is not None and iv is None:
+            raise ValueError("an encrypted store needs the archive's IV")
+        self.aes = aes
+        self.iv = iv
+        self._z = HipLz4Compressor(device=device)
+
+    def destroy(self) -> None:
+        if getattr(self, "_z", None) is not None:
+            self._z.destroy()
+            self._z = None
+        if self._own_aes and self.aes is not None:
+            self.aes.destroy()
+            self.aes = None
+
+    def read(self, map_slots, nbuf: int, slot_len: int, store, store_off, store_len, store_raw_len, pos_base: int,
+             verify: bool = False, out=None, stages=None):
+        """map_slots: device uint8, nbuf slots of slot_len bytes.  store: device uint8 holding the
+        putChunk records ``[BE32 nz][payload]`` (AES-CBC ciphertext of them when ``aes`` is set);
+        record of hashloc pos_base + k at store[store_off[k] : + store_len[k]], its chunk
+        store_raw_len[k] bytes long.  Returns (buffers uint8 [nbuf, chunk_length], status int32
+        [nbuf], :class:`ReadInfo`).  ``out``: optional uint8 [nbuf, chunk_length] to write into.  ``stages``: optional callable(name) called after each stage is
+        enqueued (measurements)."""
+        import torch
+
+        mark = stages or (lambda name: None)
+        dev = store.device
+        pairs = parse_map_slots(map_slots, nbuf, slot_len, self.hash_len, self.device)
+        mark("parse")
+        plan = plan_reads(pairs, store_off, store_len, store_raw_len, pos_base, self.device)
+        mark("plan")
+        # the one host read: the scratch sizes
+        chunk_bytes, plain_bytes = (int(v) for v in plan["total_bytes"].tolist())
+        k = int(plan["fetch_count"].item())
+        src, src_off, src_len = store, plan["src_off"][:k], plan["src_len"][:k]
+        dst_off, dst_cap = plan["dst_off"][:k], plan["dst_cap"][:k]
+        chunks = torch.empty(chunk_bytes + 64, dtype=torch.uint8, device=dev)
+        fetch_len = torch.empty(max(k, 1), dtype=torch.int32, device=dev)[:k]
+        if k and self.aes is not None:
+            plain = torch.empty(plain_bytes + 64, dtype=torch.uint8, device=dev)
+            plain_len = torch.empty(k, dtype=torch.int32, device=dev)
+            plain_off = plan["plain_off"][:k]
+            self.aes.decrypt_device(store, src_off, src_len, plain, plain_off, plain_len, iv=self.iv)
+            mark("decrypt")
+            src, src_off, src_len = plain, plain_off, chain_lens(plain_len, device=self.device)
+            mark("chain_lens")
+        if k:
+            self._z.decompress_device(src, src_off, src_len, chunks, dst_off, dst_cap, fetch_len, framed=True)
+        mark("decode")
+        if k == 0:  # assemble still needs valid pointers
+            dst_off = plan["dst_off"]
+            fetch_len = torch.zeros(1, dtype=torch.int32, device=dev)
+        out = assemble(pairs, self.chunk_length, plan["pair_fetch"], chunks, dst_off, fetch_len, out=out,
+                       device=self.device)
+        mark("assemble")
+        info = ReadInfo(k, pairs, plan["pair_fetch"])
+        if verify:
+            if self.engine is None:
+                raise ValueError("verify=True needs the hash engine")
+            if k:
+                info.pair_bad, info.bad_count = verify_reads(self.engine, pairs, plan["pair_fetch"], chunks, dst_off,
+                                                             fetch_len, plan["fetch_count"])
+            else:
+                info.pair_bad = torch.zeros((nbuf, pairs.cap), dtype=torch.uint8, device=dev)
+                info.bad_count = torch.zeros(nbuf, dtype=torch.int32, device=dev)
+            mark("verify")
+        return out, pairs.status[:nbuf], info
