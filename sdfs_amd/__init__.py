@@ -16,10 +16,11 @@ from .engine import (  # noqa: F401
     HipVariableSha256HashEngine,
     SdfsConfig,
 )
+from .archive import ArchiveSet, HipBlobArchiver, HipBufferWriter  # noqa: F401
 from .read import HipBufferReader, parse_map_slots  # noqa: F401
 
 __all__ = [
-    "HipBufferReader", "parse_map_slots",
+    "ArchiveSet", "HipBlobArchiver", "HipBufferWriter", "HipBufferReader", "parse_map_slots",
     "Finger", "HashFunctionPool", "HipVariableMD5HashEngine", "HipVariableSha256HashEngine", "SdfsConfig",
     "SdfsCdcError", "POLY", "VARIABLE_MD5", "VARIABLE_SHA256", "VARIABLE_SHA256_160",
 ]

@@ -18,7 +18,7 @@ TUNING_LIB = os.path.join(HERE, "libsdfs_cdc_tuning.so")
 LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
-                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h")]
+                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -95,6 +95,42 @@ class Pairs(ctypes.Structure):
         ("reserved", ctypes.c_uint32),
     ]
 
+
+class ArchiveLayout(ctypes.Structure):
+    """``sdfs_cdc_archive_layout`` (include/sdfs_archive.h): device pointers of where a call's records lie."""
+
+    _fields_ = [
+        ("arc", ctypes.c_void_p),
+        ("pos", ctypes.c_void_p),
+        ("store_off", ctypes.c_void_p),
+        ("arc_first", ctypes.c_void_p),
+        ("arc_bytes", ctypes.c_void_p),
+        ("arc_base", ctypes.c_void_p),
+        ("totals", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("arc_cap", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class ArchiveKept(ctypes.Structure):
+    """``sdfs_cdc_archive_kept``: what compaction lays out for the surviving records."""
+
+    _fields_ = [
+        ("new_of_old", ctypes.c_void_p),
+        ("sel", ctypes.c_void_p),
+        ("src_off", ctypes.c_void_p),
+        ("rec_len", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("deleted", ctypes.c_void_p),
+        ("new_arc", ctypes.c_void_p),
+        ("map_slots", ctypes.c_void_p),
+        ("lay", ArchiveLayout),
+    ]
+
+
+ARCHIVE_ALIGN, ARCHIVE_HEADER, ARCHIVE_NONE = 4096, 1024, 0xFFFFFFFF  # SDFS_CDC_ARCHIVE_*
+ARCHIVE_ECAP, ARCHIVE_ESTORE = 1, 2
 
 READ_CORRUPT, READ_MISSING, READ_FETCH, READ_BOUNDS = 1, 2, 4, 8  # SDFS_CDC_READ_*
 READ_NONE = 0xFFFFFFFF
@@ -201,6 +237,25 @@ SIGNATURES = {
                                               _vp, _vp, _vp, _vp]),
     "sdfs_cdc_read_verify": (ctypes.c_int, [_vp, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, _vp, _vp, _vp, _vp,
                                             _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    # include/sdfs_archive.h
+    "sdfs_cdc_archive_map_size": (ctypes.c_uint32, [ctypes.c_uint64]),
+    "sdfs_cdc_archive_pack_span": (ctypes.c_uint32, []),
+    "sdfs_cdc_archive_map_bytes": (ctypes.c_uint64, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
+    "sdfs_cdc_archive_plan": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                             _u64p, ctypes.c_uint32, ctypes.c_uint32, _P(ArchiveLayout), _vp]),
+    "sdfs_cdc_archive_pack": (ctypes.c_int, [ctypes.c_int, _P(ArchiveLayout), _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                             ctypes.c_int, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             _vp, _vp, ctypes.c_uint64, _vp]),
+    "sdfs_cdc_archive_map_emit": (ctypes.c_int, [ctypes.c_int, _P(ArchiveLayout), _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                                 ctypes.c_uint32, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp, _vp,
+                                                 _vp]),
+    "sdfs_cdc_archive_compact_select": (ctypes.c_int, [ctypes.c_int, _P(ArchiveLayout), ctypes.c_uint64, ctypes.c_uint32,
+                                                       _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
+                                                       ctypes.c_uint32, _P(ArchiveKept), _vp]),
+    "sdfs_cdc_archive_compact": (ctypes.c_int, [ctypes.c_int, _P(ArchiveLayout), ctypes.c_uint64, ctypes.c_uint32, _vp,
+                                                _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
+                                                ctypes.c_uint32, ctypes.c_uint32, _vp, _P(ArchiveKept), _vp,
+                                                ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

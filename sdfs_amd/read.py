@@ -153,9 +153,11 @@ class HipBufferReader:
     """WritableCacheBuffer.initBuffer for batches of buffers on one GPU.
 
     aes: a :class:`sdfs_amd.aes.HipEncryptUtils` (or the key bytes) when the store is encrypted, with
-    iv the archive's 16 bytes.  engine: the hash engine, needed for ``verify=True``."""
+    iv the archive's 16 bytes (record_ivs: every read brings ``store_ivs`` instead).  engine: the
+    hash engine, needed for ``verify=True``."""
 
-    def __init__(self, chunk_length: int, hash_len: int = 32, device: int = 0, aes=None, iv=None, engine=None):
+    def __init__(self, chunk_length: int, hash_len: int = 32, device: int = 0, aes=None, iv=None, engine=None,
+                 record_ivs: bool = False):
         from .lz4 import HipLz4Compressor
 
         self.chunk_length = int(chunk_length)
@@ -168,7 +170,7 @@ class HipBufferReader:
 
             aes = HipEncryptUtils(bytes(aes), device)
             self._own_aes = True
-        if aes is not None and iv is None:
+        if aes is not None and iv is None and not record_ivs:
             raise ValueError("an encrypted store needs the archive's IV")
         self.aes = aes
         self.iv = iv
@@ -183,13 +185,15 @@ class HipBufferReader:
             self.aes = None
 
     def read(self, map_slots, nbuf: int, slot_len: int, store, store_off, store_len, store_raw_len, pos_base: int,
-             verify: bool = False, out=None, stages=None):
+             verify: bool = False, out=None, stages=None, store_ivs=None):
         """map_slots: device uint8, nbuf slots of slot_len bytes.  store: device uint8 holding the
         putChunk records ``[BE32 nz][payload]`` (AES-CBC ciphertext of them when ``aes`` is set);
         record of hashloc pos_base + k at store[store_off[k] : + store_len[k]], its chunk
         store_raw_len[k] bytes long.  Returns (buffers uint8 [nbuf, chunk_length], status int32
         [nbuf], :class:`ReadInfo`).  ``out``: optional uint8 [nbuf, chunk_length] to write into.  ``stages``: optional callable(name) called after each stage is
-        enqueued (measurements)."""
+        enqueued (measurements).  ``store_ivs``: optional device uint8 [n_store, 16], the IV of each
+        directory entry's record, for a store whose archives have IVs of their own
+        (``ArchiveSet.record_ivs()``); default: ``iv`` for every record."""
         import torch
 
         mark = stages or (lambda name: None)
@@ -209,7 +213,17 @@ class HipBufferReader:
             plain = torch.empty(plain_bytes + 64, dtype=torch.uint8, device=dev)
             plain_len = torch.empty(k, dtype=torch.int32, device=dev)
             plain_off = plan["plain_off"][:k]
-            self.aes.decrypt_device(store, src_off, src_len, plain, plain_off, plain_len, iv=self.iv)
+            ivs = None
+            if store_ivs is None and self.iv is None:
+                raise ValueError("an encrypted store needs the archive's IV or store_ivs")
+            if store_ivs is not None:  # fetch f's directory entry, from any pair that uses it
+                pf = plan["pair_fetch"].view(-1)
+                used = pf >= 0
+                entry = torch.zeros(k, dtype=torch.int64, device=dev)
+                entry[pf[used].long()] = pairs.hashloc.view(-1)[used] - int(pos_base)
+                ivs = store_ivs[entry].contiguous()
+            self.aes.decrypt_device(store, src_off, src_len, plain, plain_off, plain_len,
+                                    iv=self.iv if ivs is None else None, ivs=ivs)
             mark("decrypt")
             src, src_off, src_len = plain, plain_off, chain_lens(plain_len, device=self.device)
             mark("chain_lens")
