@@ -18,7 +18,7 @@ TUNING_LIB = os.path.join(HERE, "libsdfs_cdc_tuning.so")
 LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
-                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h")]
+                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -131,6 +131,48 @@ class ArchiveKept(ctypes.Structure):
 
 ARCHIVE_ALIGN, ARCHIVE_HEADER, ARCHIVE_NONE = 4096, 1024, 0xFFFFFFFF  # SDFS_CDC_ARCHIVE_*
 ARCHIVE_ECAP, ARCHIVE_ESTORE = 1, 2
+
+
+class StoreRecords(ctypes.Structure):
+    """``sdfs_cdc_store_records`` (include/sdfs_store.h): the scan's record list."""
+
+    _fields_ = [
+        ("arc", ctypes.c_void_p),
+        ("slot", ctypes.c_void_p),
+        ("pos", ctypes.c_void_p),
+        ("len", ctypes.c_void_p),
+        ("store_off", ctypes.c_void_p),
+        ("key", ctypes.c_void_p),
+        ("raw_len", ctypes.c_void_p),
+        ("flags", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("n_cap", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class StoreArchives(ctypes.Structure):
+    """``sdfs_cdc_store_archives``: the scan's per-archive outputs."""
+
+    _fields_ = [
+        ("map_slots", ctypes.c_void_p),
+        ("version", ctypes.c_void_p),
+        ("arc_first", ctypes.c_void_p),
+        ("ivs", ctypes.c_void_p),
+        ("slot_rec", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+        ("slot_stride", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+# SDFS_CDC_STORE_*: record flags, archive status, the scan's status word
+STORE_RANGE, STORE_KEY, STORE_LEN, STORE_NZ, STORE_FETCH, STORE_HASH = 1, 2, 4, 8, 16, 32
+STORE_UNREADABLE = STORE_RANGE | STORE_LEN | STORE_NZ
+STORE_GAP, STORE_SLOTS = 1, 2
+STORE_ECAP = 1
+STORE_SORT_LDS = 16384
 
 READ_CORRUPT, READ_MISSING, READ_FETCH, READ_BOUNDS = 1, 2, 4, 8  # SDFS_CDC_READ_*
 READ_NONE = 0xFFFFFFFF
@@ -256,6 +298,18 @@ SIGNATURES = {
                                                 _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, ctypes.c_uint32,
                                                 ctypes.c_uint32, ctypes.c_uint32, _vp, _P(ArchiveKept), _vp,
                                                 ctypes.c_uint64, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    # include/sdfs_store.h
+    "sdfs_cdc_store_scan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                           ctypes.c_uint64, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                           ctypes.c_uint32, ctypes.c_int, _P(StoreRecords), _P(StoreArchives), _vp]),
+    "sdfs_cdc_store_raw_lens": (ctypes.c_int, [ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp,
+                                               _vp, _vp]),
+    "sdfs_cdc_store_directory": (ctypes.c_int, [ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                                ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_store_lookup": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                             ctypes.c_uint64, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_store_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
 }
 
 _lib = None
