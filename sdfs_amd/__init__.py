@@ -19,10 +19,11 @@ from .engine import (  # noqa: F401
 from .archive import ArchiveSet, HipBlobArchiver, HipBufferWriter  # noqa: F401
 from .read import HipBufferReader, parse_map_slots  # noqa: F401
 from .store import lookup, open_store, scan_store, scrub  # noqa: F401
+from .extent import copy_extents, rewrite_blocks, split_extent  # noqa: F401
 
 __all__ = [
     "ArchiveSet", "HipBlobArchiver", "HipBufferWriter", "HipBufferReader", "parse_map_slots",
-    "open_store", "scan_store", "lookup", "scrub",
+    "open_store", "scan_store", "lookup", "scrub", "copy_extents", "rewrite_blocks", "split_extent",
     "Finger", "HashFunctionPool", "HipVariableMD5HashEngine", "HipVariableSha256HashEngine", "SdfsConfig",
     "SdfsCdcError", "POLY", "VARIABLE_MD5", "VARIABLE_SHA256", "VARIABLE_SHA256_160",
 ]

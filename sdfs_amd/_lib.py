@@ -18,7 +18,8 @@ TUNING_LIB = os.path.join(HERE, "libsdfs_cdc_tuning.so")
 LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
-                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h")]
+                               for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h",
+                                         "sdfs_extent.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -177,6 +178,31 @@ STORE_SORT_LDS = 16384
 READ_CORRUPT, READ_MISSING, READ_FETCH, READ_BOUNDS = 1, 2, 4, 8  # SDFS_CDC_READ_*
 READ_NONE = 0xFFFFFFFF
 
+
+class Segment(ctypes.Structure):
+    """``sdfs_cdc_segment`` (include/sdfs_extent.h)."""
+
+    _fields_ = [("src_buf", ctypes.c_uint32), ("src_off", ctypes.c_uint32), ("dst_buf", ctypes.c_uint32),
+                ("dst_off", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+class Run(ctypes.Structure):
+    """``sdfs_cdc_run``."""
+
+    _fields_ = [("dst_buf", ctypes.c_uint32), ("run_pos", ctypes.c_uint32)]
+
+
+class Inserts(ctypes.Structure):
+    """``sdfs_cdc_inserts``: device pointers of an insert list."""
+
+    _fields_ = [("hash", ctypes.c_void_p), ("hashloc", ctypes.c_void_p), ("len", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("nlen", ctypes.c_void_p),
+                ("dst_buf", ctypes.c_void_p)]
+
+
+# SDFS_CDC_EXT_*
+EXT_CORRUPT, EXT_OVERLAP, EXT_BAD_INSERT, EXT_OVERFLOW, EXT_ECAP, EXT_HOLE, EXT_SRC = 1, 2, 4, 8, 16, 32, 64
+
 # (name, restype, argtypes) for every entry point of include/sdfs_cdc.h
 _P = ctypes.POINTER
 _u8p, _u32p, _u64p, _vp = _P(ctypes.c_uint8), _P(ctypes.c_uint32), _P(ctypes.c_uint64), ctypes.c_void_p
@@ -310,6 +336,16 @@ SIGNATURES = {
                                              ctypes.c_uint64, _u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                              _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdfs_cdc_store_verify": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    # include/sdfs_extent.h
+    "sdfs_cdc_map_extents": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_uint32, _vp, _vp, _P(Inserts), ctypes.c_uint64, _vp, _vp, _vp]),
+    "sdfs_cdc_map_inserts_from_chunks": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(DevOut), ctypes.c_uint32, _vp,
+                                                        ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _P(Inserts),
+                                                        ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_map_insert": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P(Pairs),
+                                           _P(Inserts), ctypes.c_uint64, _vp, _P(Pairs), _vp, _vp, _vp]),
+    "sdfs_cdc_map_emit_pairs": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, _vp, _vp,
+                                               ctypes.c_uint8, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
 }
 
 _lib = None
