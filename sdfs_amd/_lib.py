@@ -384,6 +384,18 @@ def check(rc: int) -> int:
     return rc
 
 
+def ptr(t):
+    """Device address of a tensor for a C-ABI argument; None (NULL) for an absent one."""
+    return t.data_ptr() if t is not None else None
+
+
+def stream_of(t, stream):
+    """``stream`` if given, else the current stream of tensor ``t``'s device, as a C-ABI handle."""
+    import torch
+
+    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+
+
 def default_params(backup_volume: bool = False) -> Params:
     p = Params()
     check(load().sdfs_cdc_params_default(ctypes.byref(p), 1 if backup_volume else 0))

@@ -24,7 +24,7 @@ import os
 from dataclasses import dataclass, field
 
 from . import _lib
-from ._lib import ARCHIVE_ECAP, ARCHIVE_ESTORE, ARCHIVE_HEADER, ARCHIVE_NONE, check  # noqa: F401
+from ._lib import ARCHIVE_ECAP, ARCHIVE_ESTORE, ARCHIVE_HEADER, ARCHIVE_NONE, check, ptr, stream_of  # noqa: F401
 
 MAX_LEN = 1048576 * 20  # HashBlobArchive.MAX_LEN (HashBlobArchive.java:83)
 LEN_VARIANCE = .25      # HashBlobArchive.LEN_VARIANCE (:86)
@@ -52,16 +52,6 @@ def map_bytes(map_slots: int, hash_len: int, version: int) -> int:
 
 def _r16(n: int) -> int:
     return (int(n) + 15) // 16 * 16
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream(t, stream):
-    import torch
-
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
 
 
 class Layout:
@@ -179,9 +169,9 @@ class HipBlobArchiver:
             lay = Layout(n, n if arc_cap is None else arc_cap, rec_len.device)
         blk = (ctypes.c_uint64 * len(self.blocksz))(*self.blocksz)
         hb = self.header_bytes if header_bytes is None else int(header_bytes)
-        check(self._lib.sdfs_cdc_archive_plan(self.device, _ptr(rec_len) if n else None, _ptr(count), n, self.hash_len,
+        check(self._lib.sdfs_cdc_archive_plan(self.device, ptr(rec_len) if n else None, ptr(count), n, self.hash_len,
                                               hb, blk, len(self.blocksz), self.map_slots, ctypes.byref(lay.c),
-                                              _stream(rec_len, stream)))
+                                              stream_of(rec_len, stream)))
         return lay
 
     def pack(self, lay: Layout, src, src_off, src_len, records, sel=None, count=None, ivs=None, store=None,
@@ -193,10 +183,10 @@ class HipBlobArchiver:
             store = torch.empty(_r16(store_bytes) + 16, dtype=torch.uint8, device=src.device)
         cap = store.numel() if store_bytes is None else int(store_bytes)
         hb = self.header_bytes if header_bytes is None else int(header_bytes)
-        check(self._lib.sdfs_cdc_archive_pack(self.device, ctypes.byref(lay.c), _ptr(count), int(src_len.shape[0]),
+        check(self._lib.sdfs_cdc_archive_pack(self.device, ctypes.byref(lay.c), ptr(count), int(src_len.shape[0]),
                                               src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), int(raw_frame),
-                                              records.data_ptr(), _ptr(sel), self.hash_len, hb, self.version,
-                                              _ptr(ivs), store.data_ptr(), cap, _stream(src, stream)))
+                                              records.data_ptr(), ptr(sel), self.hash_len, hb, self.version,
+                                              ptr(ivs), store.data_ptr(), cap, stream_of(src, stream)))
         return store
 
     def map_emit(self, lay: Layout, rec_len, records, sel=None, count=None, n_arc: int | None = None,
@@ -213,10 +203,10 @@ class HipBlobArchiver:
         info = torch.zeros(2, dtype=torch.int64, device=dev)
         c = _lib.ArchiveLayout.from_buffer_copy(lay.c)
         c.arc_cap = rows if n_arc is not None else lay.arc_cap
-        check(self._lib.sdfs_cdc_archive_map_emit(self.device, ctypes.byref(c), _ptr(count), int(rec_len.shape[0]),
-                                                  rec_len.data_ptr(), records.data_ptr(), _ptr(sel), self.hash_len,
-                                                  self.version, _ptr(map_sizes), stride, maps.data_ptr(),
-                                                  slot_rec.data_ptr(), info.data_ptr(), _stream(rec_len, stream)))
+        check(self._lib.sdfs_cdc_archive_map_emit(self.device, ctypes.byref(c), ptr(count), int(rec_len.shape[0]),
+                                                  rec_len.data_ptr(), records.data_ptr(), ptr(sel), self.hash_len,
+                                                  self.version, ptr(map_sizes), stride, maps.data_ptr(),
+                                                  slot_rec.data_ptr(), info.data_ptr(), stream_of(rec_len, stream)))
         return maps, slot_rec, info
 
     # ---- a batch of records to an ArchiveSet
@@ -275,10 +265,10 @@ class HipBlobArchiver:
         keep = keep.to(torch.uint8).contiguous()
         old = arcs.layout
         oc = _lib.ArchiveLayout.from_buffer_copy(old.c)
-        s = _stream(arcs.store, None)
+        s = stream_of(arcs.store, None)
         stride = map_size(2 * arcs.max_entries + 5)
         head = (self.device, ctypes.byref(oc), n, n_arc)
-        old_maps = (arcs.rec_len.data_ptr(), _ptr(arcs.sel), arcs.slot_rec.data_ptr(), _ptr(arcs.map_sizes),
+        old_maps = (arcs.rec_len.data_ptr(), ptr(arcs.sel), arcs.slot_rec.data_ptr(), ptr(arcs.map_sizes),
                     arcs.map_stride, keep.data_ptr())
         if not arcs.header_bytes:
             store = torch.empty(_r16(arcs.store_bytes) + 16, dtype=torch.uint8, device=dev)

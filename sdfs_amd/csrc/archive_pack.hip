@@ -31,7 +31,9 @@
 #include <cstdint>
 
 #include "../../include/sdfs_archive.h"
-#include "cdc_internal.h"
+#include "block_scan.h"
+#include "call_support.h"
+#include "store_format.h"
 
 namespace sdfs {
 namespace {
@@ -44,37 +46,6 @@ constexpr uint32_t kPackVecs = 4096;     // 16-byte vectors per workgroup (64 Ki
 constexpr uint32_t kPackLdsRecs = 1024;  // records of a span staged in LDS (28 KiB)
 constexpr int kMapThreads = 1024;
 constexpr uint32_t kMapLdsSlots = 15360;  // owner table in LDS (60 KiB): map_size(2 * 0.75 * MAX_HM_SZ + 5) of a compaction fits
-
-__host__ __device__ inline uint32_t map_size_rule(uint64_t sz) {
-    if (sz <= 2) return 2;
-    for (uint32_t k = 3; k < 9; k += 2)
-        if (sz <= k) return k;
-    if (sz > (uint64_t)INT32_MAX) return 0;  // the next prime would pass Integer.MAX_VALUE (itself prime)
-    if ((sz & 1) == 0) sz += 1;
-    for (uint64_t i = sz;; i += 2) {
-        bool prime = true;
-        for (uint64_t j = 3; j * j <= i; j += 2)
-            if (i % j == 0) {
-                prime = false;
-                break;
-            }
-        if (prime) return (uint32_t)i;
-    }
-}
-
-__host__ __device__ inline uint32_t map_entry_bytes(uint32_t hash_len, uint32_t version) {
-    return hash_len + (version ? 8u : 4u);
-}
-
-__host__ __device__ inline uint64_t map_image_bytes(uint32_t slots, uint32_t hash_len, uint32_t version) {
-    return (version ? 16u : 0u) + (uint64_t)slots * map_entry_bytes(hash_len, version);
-}
-
-__device__ __forceinline__ uint32_t be_byte(uint32_t v, uint32_t k) { return (v >> (8 * (3 - k))) & 255u; }
-
-__device__ __forceinline__ uint64_t live_count(const uint32_t* count, uint64_t n_max) {
-    return count ? min<uint64_t>(*count, n_max) : n_max;
-}
 
 // ----------------------------------------------------------------------------------------- plan
 
@@ -98,18 +69,13 @@ __global__ __launch_bounds__(kPlanThreads) void archive_plan_kernel(PlanArgs a) 
     __shared__ uint32_t s_narc, s_fail;
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint64_t n = live_count(a.count, a.n_max);
-    const uint32_t unit = 8 + a.hash_len;
+    const uint32_t unit = record_header_bytes(a.hash_len);
     // exclusive prefix of unit + len, tile by tile
     uint64_t carry = 0;
     for (uint64_t i0 = 0; i0 < n; i0 += kPlanThreads) {
         const uint64_t i = i0 + t;
         const uint64_t v = i < n ? (uint64_t)unit + a.rec_len[i] : 0;
-        uint64_t inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long y = __shfl_up((unsigned long long)inc, o);
-            if (lane >= (uint32_t)o) inc += y;
-        }
+        const uint64_t inc = wave_inclusive_scan(v, lane);
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         uint64_t before = carry, tile = 0;
@@ -235,19 +201,6 @@ struct RecView {
     int32_t n;
 };
 
-// largest j with so[j] - hp <= x, -1 if none; `hint` = the answer for a nearby x
-__device__ __forceinline__ int32_t floor_rec(const RecView& v, uint64_t xh, int32_t hint) {
-    if (hint >= -1 && hint < v.n && (hint < 0 || v.so[hint] <= xh) && (hint + 1 >= v.n || v.so[hint + 1] > xh))
-        return hint;
-    int32_t lo = 0, hi = v.n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (v.so[mid] <= xh) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;
-}
-
 // byte x of the store: where it comes from (p != NULL: that byte; else the constant c); j = floor
 // record of some x' <= x.  Only LDS is read on the way (arc_base for an archive header aside), so a
 // vector's 16 sources are known before the first of its loads is issued.
@@ -258,21 +211,21 @@ struct ByteSrc {
 
 __device__ __forceinline__ ByteSrc pack_byte(const PackArgs& a, const RecView& v, uint64_t x, int32_t& j,
                                              uint32_t n_arc) {
-    const uint32_t hp = 8 + a.hash_len;
+    const uint32_t hp = record_header_bytes(a.hash_len);
     while (j + 1 < v.n && v.so[j + 1] <= x + hp) j++;
     uint32_t next_arc = 0;
     if (j >= 0) {
         uint64_t k = x + hp - v.so[j];
         const uint32_t len = v.len[j];
         if (k < (uint64_t)hp + a.raw_frame + len) {
-            if (k < 4) return {nullptr, be_byte(a.hash_len, (uint32_t)k)};
+            if (k < 4) return {nullptr, be32_byte(a.hash_len, (uint32_t)k)};
             k -= 4;
             if (k < a.hash_len) {
                 const uint64_t r = v.sel ? v.sel[j] : (uint64_t)(v.base + j);
                 return {a.records + r * kRecordBytes + k, 0};
             }
             k -= a.hash_len;
-            if (k < 4) return {nullptr, be_byte(len + a.raw_frame, (uint32_t)k)};
+            if (k < 4) return {nullptr, be32_byte(len + a.raw_frame, (uint32_t)k)};
             k -= 4;
             if (k < a.raw_frame) return {nullptr, 0xFF};  // nz = -1
             return {a.src + v.src[j] + (k - a.raw_frame), 0};
@@ -283,7 +236,7 @@ __device__ __forceinline__ ByteSrc pack_byte(const PackArgs& a, const RecView& v
         const uint64_t base = a.l.arc_base[next_arc];
         if (x >= base) {
             const uint64_t k = x - base;
-            if (k < 4) return {nullptr, be_byte(a.version, (uint32_t)k)};
+            if (k < 4) return {nullptr, be32_byte(a.version, (uint32_t)k)};
             if (k < 20) return {a.ivs + (uint64_t)next_arc * 16 + (k - 4), 0};
         }
     }
@@ -299,7 +252,7 @@ __global__ __launch_bounds__(kPackThreads) void archive_pack_kernel(PackArgs a) 
     const uint32_t n_arc = (uint32_t)a.l.totals[0];
     const int64_t n = (int64_t)live_count(a.count, a.n_max);
     const uint32_t tid = threadIdx.x;
-    const uint32_t hp = 8 + a.hash_len;
+    const uint32_t hp = record_header_bytes(a.hash_len);
     const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(a.store) & 15);
     const uint64_t nvec = ((uint64_t)head + sb + 15) / 16;  // vectors at absolute 16-byte addresses
     const uint64_t v0 = (uint64_t)blockIdx.x * kPackVecs;
@@ -308,7 +261,9 @@ __global__ __launch_bounds__(kPackThreads) void archive_pack_kernel(PackArgs a) 
     const uint64_t x_lo = v0 * 16 > head ? v0 * 16 - head : 0, x_hi = min(sb, v1 * 16 - head);  // the span's bytes
     // the span's records: floor record of its first byte .. floor record of its last byte
     RecView all{a.l.store_off, a.src_off, a.src_len, a.l.arc, a.sel, 0, (int32_t)min<int64_t>(n, INT32_MAX)};
-    const int32_t r0 = max(floor_rec(all, x_lo + hp, -2), 0), r1 = floor_rec(all, x_hi - 1 + hp, -2);
+    // (floor record of byte x: the largest j with so[j] - hp <= x)
+    const int32_t r0 = max(floor_index(all.so, all.n, x_lo + hp, -2), 0);
+    const int32_t r1 = floor_index(all.so, all.n, x_hi - 1 + hp, -2);
     RecView rv{a.l.store_off + r0, a.src_off + r0, a.src_len + r0, a.l.arc + r0, a.sel ? a.sel + r0 : nullptr,
                r0, max(r1 - r0 + 1, 0)};
     if (rv.n <= (int32_t)kPackLdsRecs) {
@@ -346,7 +301,7 @@ __global__ __launch_bounds__(kPackThreads) void archive_pack_kernel(PackArgs a) 
             if (v >= v1) continue;
             const int64_t o = (int64_t)(v * 16) - head;  // store offset of the vector's first byte
             const uint64_t x0 = (uint64_t)max<int64_t>(o, 0);
-            j = floor_rec(rv, x0 + hp, j);
+            j = floor_index(rv.so, rv.n, x0 + hp, j);
             jf[it] = j;
             if (o < 0 || (uint64_t)o + 16 > sb) {  // a store end that is not 16-byte aligned
                 mode[it] = kEdge;
@@ -440,10 +395,6 @@ __device__ __forceinline__ const uint8_t* rec_key(const MapArgs& a, uint32_t r) 
     return a.records + (uint64_t)(a.sel ? a.sel[r] : r) * kRecordBytes;
 }
 
-__device__ __forceinline__ uint32_t key_hash(const uint8_t* key) {
-    return ((uint32_t)key[8] << 24 | (uint32_t)key[9] << 16 | (uint32_t)key[10] << 8 | (uint32_t)key[11]) & 0x7fffffffu;
-}
-
 template <bool LDS>
 __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
     __shared__ uint32_t s_owner[LDS ? kMapLdsSlots : 1];
@@ -466,8 +417,8 @@ __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
         for (uint32_t r0 = first + t; r0 < last; r0 += kMapThreads) {
             uint32_t cur = r0;
             const uint8_t* key = rec_key(a, cur);
-            uint32_t h = key_hash(key);
-            uint32_t idx = h % size;
+            uint32_t h = map_key_hash(key);
+            uint32_t idx = map_probe_home(h, size);
             for (uint64_t guard = 0; guard < 2ull * size * cnt + 2; guard++) {
                 const uint32_t old = atomicMin(&owner[idx], cur);
                 if (old == kNone) break;
@@ -484,10 +435,9 @@ __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
                 if (mover != cur) {
                     cur = mover;
                     key = ko;
-                    h = key_hash(key);
+                    h = map_key_hash(key);
                 }
-                const uint32_t step = 1 + h % (size - 2);
-                idx = idx >= step ? idx - step : idx + size - step;
+                idx = map_probe_next(idx, map_probe_step(h, size), size);
             }
         }
     }
@@ -496,8 +446,9 @@ __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
         if (LDS) row[s] = s < size ? owner[s] : kNone;
         else if (s >= size) row[s] = kNone;
     }
-    // the image, one 32-bit word per thread (every field is 4-byte aligned)
-    const uint32_t el = map_entry_bytes(a.hash_len, a.version), off = a.version ? 16 : 0;
+    // the image, one 32-bit word per thread (every field is 4-byte aligned): __builtin_bswap32(v) is
+    // the word whose bytes in memory are put_be32(v)
+    const uint32_t el = map_entry_bytes(a.hash_len, a.version), off = map_header_bytes(a.version);
     const uint64_t stride_bytes = map_image_bytes(a.stride, a.hash_len, a.version);
     const uint64_t image_bytes = map_image_bytes(size, a.hash_len, a.version);
     uint32_t* img = reinterpret_cast<uint32_t*>(a.maps + (uint64_t)arc * stride_bytes);
@@ -505,7 +456,8 @@ __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
         const uint64_t b = w * 4;
         uint32_t val = 0;
         if (b < off) {
-            val = b == 0 ? __builtin_bswap32(SDFS_CDC_ARCHIVE_MAP_MAGIC) : b == 4 ? __builtin_bswap32(a.version) : 0;
+            val = b == 0 ? __builtin_bswap32(SDFS_CDC_ARCHIVE_MAP_MAGIC)
+                         : b == kMapVersionAt ? __builtin_bswap32(a.version) : 0;
         } else if (b < image_bytes) {
             const uint32_t s = (uint32_t)((b - off) / el), k = (uint32_t)((b - off) % el);
             const uint32_t r = owner[s];
@@ -513,9 +465,9 @@ __global__ __launch_bounds__(kMapThreads) void archive_map_kernel(MapArgs a) {
                 if (k < a.hash_len) {
                     const uint8_t* key = rec_key(a, r) + k;
                     val = (uint32_t)key[0] | (uint32_t)key[1] << 8 | (uint32_t)key[2] << 16 | (uint32_t)key[3] << 24;
-                } else if (k == a.hash_len) {
-                    val = __builtin_bswap32(a.l.pos[r] - 4);
-                } else {
+                } else if (k == a.hash_len + kMapPosAt) {
+                    val = __builtin_bswap32(a.l.pos[r] - kRecordLenBack);  // the map value: the length word's place
+                } else {  // a.hash_len + kMapLenAt
                     val = __builtin_bswap32(a.rec_len[r]);
                 }
             }
@@ -591,7 +543,7 @@ __global__ __launch_bounds__(256) void compact_assign_kernel(SelectArgs a) {
     for (uint32_t s0 = 0; s0 < size; s0 += 256) {
         uint32_t r;
         const bool on = slot_kept(a, arc, s0 + t, size, r);
-        const uint64_t m = __ballot(on);
+        const uint64_t m = __ballot(on);  // a flag's wave scan is one ballot, not a wave_inclusive_scan
         const uint32_t below = __popcll(m & ((1ull << lane) - 1));
         if (lane == 0) ws[wave] = __popcll(m);
         __syncthreads();
@@ -625,51 +577,10 @@ bool kept_complete(const sdfs_cdc_archive_kept* k) {
            k->map_slots && layout_complete(&k->lay);
 }
 
-// per-call scratch in stream order; released in the destructor (the frees are enqueued behind
-// whatever was launched on the stream before it runs)
-struct Scratch {
-    hipStream_t s;
-    void* ptrs[6] = {};
-    int n = 0;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    template <typename T>
-    hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMallocAsync(&p, std::max<size_t>(count, 1) * sizeof(T), s);
-        if (e == hipSuccess) ptrs[n++] = p;
-        *out = static_cast<T*>(p);
-        return e;
-    }
-    ~Scratch() {
-        for (int i = 0; i < n; i++) (void)hipFreeAsync(ptrs[i], s);
-    }
-};
-
-#define AR_TRY(expr)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                      \
-            return fail_status(e_ == hipErrorOutOfMemory ? SDFS_CDC_ENOMEM : SDFS_CDC_EHIP, "%s: %s", #expr, \
-                               hipGetErrorString(e_));                                             \
-    } while (0)
-
-int set_device(int device) {
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_status(SDFS_CDC_ENODEV, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-    return SDFS_CDC_OK;
-}
-
-int check_hash_len(uint32_t hash_len, bool map) {
-    if (hash_len == 16 || hash_len == 32 || (!map && hash_len == 20)) return SDFS_CDC_OK;
-    if (map && hash_len == 20)
-        return fail_status(SDFS_CDC_EINVAL,
-                           "hash_len 20: the reference's map slots are made for hashLength 18 and do not hold the key");
-    return fail_status(SDFS_CDC_EINVAL, "hash_len %u: 16 (MD5), 20 (SHA-256/160) or 32 (SHA-256)", hash_len);
-}
-
-int check_header(uint32_t header_bytes) {
-    if (header_bytes == 0 || header_bytes == SDFS_CDC_ARCHIVE_HEADER) return SDFS_CDC_OK;
-    return fail_status(SDFS_CDC_EINVAL, "header_bytes %u: 0 (VERSION 0) or %u", header_bytes, SDFS_CDC_ARCHIVE_HEADER);
+// a map key that is also a stored record's hash: 16 or 32; 20 gets the map's message, any other
+// length the record's
+int check_map_key_len(uint32_t hash_len) {
+    return check_hash_len(hash_len, hash_len == 20 ? HashOf::kMapKey : HashOf::kRecord);
 }
 
 // the plan kernel over `rec_len`; fixed_n_arc != NULL: the cuts are in out->arc_first already
@@ -688,10 +599,10 @@ int launch_plan(const uint32_t* d_rec_len, const uint32_t* d_count, uint64_t n_m
     a.limit = limit;
     a.o = out;
     a.fixed_n_arc = fixed_n_arc;
-    AR_TRY(sc.get(&a.prefix, (size_t)n_max + 1));
-    AR_TRY(sc.get(&a.cuts, (size_t)out.arc_cap + 1));
+    SDFS_TRY(sc.get(&a.prefix, (size_t)n_max + 1));
+    SDFS_TRY(sc.get(&a.cuts, (size_t)out.arc_cap + 1));
     hipLaunchKernelGGL(archive_plan_kernel, dim3(1), dim3(kPlanThreads), 0, s, a);
-    AR_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -714,7 +625,7 @@ int sdfs_cdc_archive_plan(int device, const uint32_t* d_rec_len, const uint32_t*
                           uint32_t hash_len, uint32_t header_bytes, const uint64_t* blocksz, uint32_t n_blocksz,
                           uint32_t map_slots, const sdfs_cdc_archive_layout* out, void* stream) {
     if (!layout_complete(out)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_layout");
-    if (const int rc = check_hash_len(hash_len, false)) return rc;
+    if (const int rc = check_hash_len(hash_len, HashOf::kRecord)) return rc;
     if (const int rc = check_header(header_bytes)) return rc;
     if (n_max && !d_rec_len) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (n_max >= UINT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n_max %llu: record ordinals are 32-bit",
@@ -743,7 +654,7 @@ int sdfs_cdc_archive_pack(int device, const sdfs_cdc_archive_layout* layout, con
                           const uint32_t* d_sel, uint32_t hash_len, uint32_t header_bytes, uint32_t version,
                           const uint8_t* d_ivs, uint8_t* d_store, uint64_t store_cap, void* stream) {
     if (!layout_complete(layout)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_layout");
-    if (const int rc = check_hash_len(hash_len, false)) return rc;
+    if (const int rc = check_hash_len(hash_len, HashOf::kRecord)) return rc;
     if (const int rc = check_header(header_bytes)) return rc;
     if (n_max && (!d_src || !d_src_off || !d_src_len || !d_records)) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (n_max >= (uint64_t)INT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n_max %llu: record ordinals are 32-bit",
@@ -761,7 +672,7 @@ int sdfs_cdc_archive_pack(int device, const sdfs_cdc_archive_layout* layout, con
     hipLaunchKernelGGL(archive_pack_check_kernel, dim3(1), dim3(1), 0, s, *layout, store_cap);
     if (store_cap && n_max)
         hipLaunchKernelGGL(archive_pack_kernel, dim3((uint32_t)blocks), dim3(kPackThreads), 0, s, a);
-    AR_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -771,7 +682,7 @@ int sdfs_cdc_archive_map_emit(int device, const sdfs_cdc_archive_layout* layout,
                               const uint32_t* d_map_slots, uint32_t map_slots, uint8_t* d_maps,
                               uint32_t* d_slot_rec, uint64_t* d_info, void* stream) {
     if (!layout_complete(layout)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_layout");
-    if (const int rc = check_hash_len(hash_len, true)) return rc;
+    if (const int rc = check_map_key_len(hash_len)) return rc;
     if (!d_maps || !d_slot_rec || !d_info) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (n_max && (!d_rec_len || !d_records)) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (n_max >= UINT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n_max %llu: record ordinals are 32-bit",
@@ -781,14 +692,14 @@ int sdfs_cdc_archive_map_emit(int device, const sdfs_cdc_archive_layout* layout,
     if (reinterpret_cast<uintptr_t>(d_maps) & 3) return fail_status(SDFS_CDC_EINVAL, "d_maps is not 4-byte aligned");
     if (const int rc = set_device(device)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    AR_TRY(hipMemsetAsync(d_info, 0, 16, s));
+    SDFS_TRY(hipMemsetAsync(d_info, 0, 16, s));
     MapArgs a{*layout, d_count, n_max, d_rec_len, d_records, d_sel, hash_len, version, d_map_slots, map_slots,
               d_maps, d_slot_rec, reinterpret_cast<unsigned long long*>(d_info)};
     if (map_slots <= kMapLdsSlots)
         hipLaunchKernelGGL(archive_map_kernel<true>, dim3(layout->arc_cap), dim3(kMapThreads), 0, s, a);
     else
         hipLaunchKernelGGL(archive_map_kernel<false>, dim3(layout->arc_cap), dim3(kMapThreads), 0, s, a);
-    AR_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -799,7 +710,7 @@ int sdfs_cdc_archive_compact_select(int device, const sdfs_cdc_archive_layout* o
                                     uint32_t header_bytes, const sdfs_cdc_archive_kept* kept, void* stream) {
     if (!layout_complete(old_layout)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_layout");
     if (!kept_complete(kept)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_kept");
-    if (const int rc = check_hash_len(hash_len, false)) return rc;
+    if (const int rc = check_hash_len(hash_len, HashOf::kRecord)) return rc;
     if (const int rc = check_header(header_bytes)) return rc;
     if (n >= UINT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n %llu: record ordinals are 32-bit", (unsigned long long)n);
     if (n_arc > old_layout->arc_cap) return fail_status(SDFS_CDC_EINVAL, "n_arc %u above the old layout's arc_cap", n_arc);
@@ -812,12 +723,12 @@ int sdfs_cdc_archive_compact_select(int device, const sdfs_cdc_archive_layout* o
     Scratch sc(s);
     SelectArgs a{*old_layout, n, n_arc, d_old_rec_len, d_old_sel, d_slot_rec, d_old_map_slots, old_map_slots,
                  d_keep, *kept, nullptr, nullptr};
-    AR_TRY(sc.get(&a.live, n_arc));
-    AR_TRY(sc.get(&a.new_first, n_arc));
+    SDFS_TRY(sc.get(&a.live, n_arc));
+    SDFS_TRY(sc.get(&a.new_first, n_arc));
     if (n_arc) hipLaunchKernelGGL(compact_count_kernel, dim3(n_arc), dim3(256), 0, s, a);
     hipLaunchKernelGGL(compact_cuts_kernel, dim3(1), dim3(1), 0, s, a);
     if (n_arc) hipLaunchKernelGGL(compact_assign_kernel, dim3(n_arc), dim3(256), 0, s, a);
-    AR_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     // the plan with fixed cuts: n_arc comes from totals[0], which the plan rewrites with the same value
     return launch_plan(kept->rec_len, kept->count, n, hash_len, header_bytes, nullptr, 0, 0, kept->lay,
                        reinterpret_cast<const uint32_t*>(kept->lay.totals), s);
@@ -832,7 +743,7 @@ int sdfs_cdc_archive_compact(int device, const sdfs_cdc_archive_layout* old_layo
                              uint32_t new_map_stride, uint8_t* d_maps, uint32_t* d_slot_rec_new, uint64_t* d_info,
                              void* stream) {
     if (!kept_complete(kept)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_archive_kept");
-    if (const int rc = check_hash_len(hash_len, true)) return rc;
+    if (const int rc = check_map_key_len(hash_len)) return rc;
     if (n && (!d_old_store || !d_records)) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (const int rc = sdfs_cdc_archive_compact_select(device, old_layout, n, n_arc, d_old_rec_len, d_old_sel,
                                                        d_slot_rec, d_old_map_slots, old_map_slots, d_keep, hash_len,

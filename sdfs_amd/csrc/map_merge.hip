@@ -18,7 +18,9 @@
 #include <cstdint>
 
 #include "../../include/sdfs_extent.h"
-#include "cdc_internal.h"
+#include "block_scan.h"
+#include "call_support.h"
+#include "store_format.h"
 
 namespace sdfs {
 namespace {
@@ -31,42 +33,11 @@ struct Work {
     int32_t pos, offset, nlen;
 };
 
-__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v) {
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
-}
-
 __device__ __forceinline__ void copy_hash(uint8_t* dst, const uint8_t* src) {
     const uint32_t* s = reinterpret_cast<const uint32_t*>(src);
     uint32_t* d = reinterpret_cast<uint32_t*>(dst);
 #pragma unroll
     for (int k = 0; k < 8; k++) d[k] = s[k];
-}
-
-// out[i] = sum of in[0..i) for i <= n (one block)
-__global__ __launch_bounds__(1024) void prefix_kernel(const uint32_t* in, uint32_t n, uint32_t* out) {
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (n + 1023) / 1024;
-    const uint32_t b0 = min(t * per, n), b1 = min(b0 + per, n);
-    uint32_t sum = 0;
-    for (uint32_t b = b0; b < b1; b++) sum += in[b];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        const uint32_t v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (uint32_t b = b0; b < b1; b++) {
-        out[b] = run;
-        run += in[b];
-    }
-    if (t == 1023) out[n] = part[1023];
 }
 
 // a pair list the edits can work on: fields in range, ascending, disjoint
@@ -401,9 +372,7 @@ __global__ __launch_bounds__(256) void emit_pairs_kernel(EmitArgs a) {
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= a.nbuf) return;
     const uint32_t n = a.p.counts[b];
-    const uint32_t bal = a.hash_len + 24;
-    const uint64_t need = 13ull + (uint64_t)n * bal;
-    if ((a.status && a.status[b]) || need > a.slot_bytes || n > a.p.cap) {
+    if ((a.status && a.status[b]) || slot_need(n, a.hash_len) > a.slot_bytes || n > a.p.cap) {
         if (lane == 0) atomicAdd(a.skipped, 1u);
         return;
     }
@@ -412,78 +381,23 @@ __global__ __launch_bounds__(256) void emit_pairs_kernel(EmitArgs a) {
     uint32_t doop = 0;
     for (uint32_t i = lane; i < n; i += 64) {
         const uint64_t slot = base + i;
-        uint8_t* p = img + 9 + (uint64_t)i * bal;
-        const uint8_t* d = a.p.hashes + slot * 32;
-        for (uint32_t k = 0; k < a.hash_len; k++) p[k] = d[k];
-        p += a.hash_len;
-        const uint64_t hl = a.p.hashloc[slot];
         const uint32_t nl = (uint32_t)a.p.nlen[slot];
-        put_be32(p, (uint32_t)(hl >> 32));
-        put_be32(p + 4, (uint32_t)hl);
-        put_be32(p + 8, (uint32_t)a.p.len[slot]);
-        put_be32(p + 12, (uint32_t)a.p.pos[slot]);
-        put_be32(p + 16, (uint32_t)a.p.offset[slot]);
-        put_be32(p + 20, nl);
+        put_pair_record(img, i, a.hash_len, a.p.hashes + slot * 32, a.p.hashloc[slot], (uint32_t)a.p.len[slot],
+                        (uint32_t)a.p.pos[slot], (uint32_t)a.p.offset[slot], nl);
         if (a.dup && a.dup[slot]) doop += nl;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) doop += __shfl_xor(doop, o);
     if (lane == 0) {
-        img[0] = a.flags;
-        put_be32(img + 1, (uint32_t)need);
-        put_be32(img + 5, n);
-        put_be32(img + 9 + (uint64_t)n * bal, doop);
+        put_slot_frame(img, a.flags, n, a.hash_len, doop);
         if (a.doop) a.doop[b] = doop;
     }
 }
 
 // ------------------------------------------------------------------------------------------ host
 
-bool pairs_complete(const sdfs_cdc_pairs* p) {
-    return p && p->counts && p->hashes && p->hashloc && p->len && p->pos && p->offset && p->nlen && p->doop &&
-           p->flags && p->status && p->cap;
-}
-
 bool inserts_complete(const sdfs_cdc_inserts* i) {
     return i && i->hash && i->hashloc && i->len && i->pos && i->offset && i->nlen && i->dst_buf;
-}
-
-struct Scratch {
-    hipStream_t s;
-    void* ptrs[6] = {};
-    int n = 0;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    template <typename T>
-    hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMallocAsync(&p, std::max<size_t>(count, 1) * sizeof(T), s);
-        if (e == hipSuccess) ptrs[n++] = p;
-        *out = static_cast<T*>(p);
-        return e;
-    }
-    ~Scratch() {
-        for (int i = 0; i < n; i++) (void)hipFreeAsync(ptrs[i], s);
-    }
-};
-
-#define MM_TRY(expr)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                      \
-            return fail_status(e_ == hipErrorOutOfMemory ? SDFS_CDC_ENOMEM : SDFS_CDC_EHIP, "%s: %s", #expr, \
-                               hipGetErrorString(e_));                                             \
-    } while (0)
-
-int set_device(int device) {
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_status(SDFS_CDC_ENODEV, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-    return SDFS_CDC_OK;
-}
-
-int check_chunk_length(uint32_t chunk_length) {
-    if (chunk_length < 1 || chunk_length > (uint32_t)INT32_MAX)
-        return fail_status(SDFS_CDC_EINVAL, "chunk_length %u: 1 .. 2^31 - 1 (HashLocPair.pos is an int)", chunk_length);
-    return SDFS_CDC_OK;
 }
 
 }  // namespace
@@ -514,16 +428,16 @@ int sdfs_cdc_map_extents(int device, uint32_t nbuf_src, const sdfs_cdc_pairs* sr
     if (const int rc = set_device(device)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (n_seg == 0) {
-        MM_TRY(hipMemsetAsync(d_seg_first, 0, 4, st));
+        SDFS_TRY(hipMemsetAsync(d_seg_first, 0, 4, st));
         return SDFS_CDC_OK;
     }
     Scratch sc(st);
     ExtArgs a{*src, nbuf_src, nbuf_dst, chunk_length, n_seg, d_segs, *ins, n_ins_cap, nullptr, d_seg_first, d_seg_status};
-    MM_TRY(sc.get(&a.seg_cnt, n_seg));
+    SDFS_TRY(sc.get(&a.seg_cnt, n_seg));
     hipLaunchKernelGGL(extents_kernel<false>, dim3(n_seg), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, st, a.seg_cnt, n_seg, d_seg_first);
+    hipLaunchKernelGGL(prefix_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, a.seg_cnt, n_seg, d_seg_first);
     hipLaunchKernelGGL(extents_kernel<true>, dim3(n_seg), dim3(64), 0, st, a);
-    MM_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -546,12 +460,12 @@ int sdfs_cdc_map_inserts_from_chunks(int device, uint32_t n_run, const sdfs_cdc_
                                h_runs[r].dst_buf, nbuf_dst, h_runs[r].run_pos, run_len, chunk_length);
     if (const int rc = set_device(device)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, st, out->counts, n_run, d_run_first);
+    hipLaunchKernelGGL(prefix_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, out->counts, n_run, d_run_first);
     if (n_run) {
         RunArgs a{n_run, *out, d_hashloc, d_runs, *ins, n_ins_cap, d_run_first};
         hipLaunchKernelGGL(from_chunks_kernel, dim3((n_run + 3) / 4), dim3(256), 0, st, a);
     }
-    MM_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -576,14 +490,14 @@ int sdfs_cdc_map_insert(int device, uint32_t nbuf, uint32_t chunk_length, uint32
     Scratch sc(st);
     InsArgs a{nbuf, chunk_length, slot_pairs, *in, *ins, n_ins, d_ins_first, *out, d_out_dup, d_status,
               nullptr, nullptr, nullptr, work};
-    MM_TRY(sc.get(&a.need, (size_t)nbuf + 1));
-    MM_TRY(sc.get(&a.need_first, (size_t)nbuf + 1));
-    MM_TRY(sc.get(&a.work, (size_t)work * 2));
+    SDFS_TRY(sc.get(&a.need, (size_t)nbuf + 1));
+    SDFS_TRY(sc.get(&a.need_first, (size_t)nbuf + 1));
+    SDFS_TRY(sc.get(&a.work, (size_t)work * 2));
     hipLaunchKernelGGL(insert_need_kernel, dim3((nbuf + 255) / 256), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(prefix_kernel, dim3(1), dim3(1024), 0, st, a.need, nbuf, a.need_first);
+    hipLaunchKernelGGL(prefix_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, a.need, nbuf, a.need_first);
     hipLaunchKernelGGL(map_insert_kernel<true>, dim3(nbuf), dim3(64), 0, st, a);
     hipLaunchKernelGGL(map_insert_kernel<false>, dim3(nbuf), dim3(256), 0, st, a);
-    MM_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -591,15 +505,14 @@ int sdfs_cdc_map_emit_pairs(int device, uint32_t nbuf, const sdfs_cdc_pairs* pai
                             const uint8_t* d_dup, const uint32_t* d_status, uint8_t flags, uint8_t* d_map,
                             uint32_t slot_bytes, uint32_t* d_doop, uint32_t* d_skipped, void* stream) {
     if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
-    if (hash_len != 32 && hash_len != 16)
-        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: HashLocPair holds 32 (SHA-256) or 16 (MD5) bytes", hash_len);
-    if (slot_bytes < 13) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
+    if (const int rc = check_hash_len(hash_len, HashOf::kPair)) return rc;
+    if (slot_bytes < kSlotFixedBytes) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
     if (nbuf && (!d_map || !d_skipped)) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (nbuf == 0) return SDFS_CDC_OK;
     if (const int rc = set_device(device)) return rc;
     EmitArgs a{nbuf, *pairs, hash_len, d_dup, d_status, flags, d_map, slot_bytes, d_doop, d_skipped};
     hipLaunchKernelGGL(emit_pairs_kernel, dim3((nbuf + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    MM_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 

@@ -29,7 +29,9 @@
 #include <cstdint>
 
 #include "../../include/sdfs_read.h"
-#include "cdc_internal.h"
+#include "block_scan.h"
+#include "call_support.h"
+#include "store_format.h"
 
 namespace sdfs {
 namespace {
@@ -38,10 +40,6 @@ constexpr uint32_t kNone = SDFS_CDC_READ_NONE;
 constexpr int kGatherThreads = 256;
 constexpr uint32_t kTileVecs = 4096;  // 16-byte vectors per workgroup (64 KiB): 4 groups of 4 per lane
 constexpr uint32_t kLdsPairs = 1024;  // used pairs per buffer staged in LDS (20 KiB)
-
-__device__ __forceinline__ uint32_t get_be32(const uint8_t* p) {
-    return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
-}
 
 __device__ __forceinline__ bool wave_any(bool v) { return __ballot(v) != 0; }
 
@@ -62,11 +60,11 @@ __device__ __forceinline__ void put_pair(const ParseArgs& a, const uint8_t* rec,
     for (uint32_t k = 0; k < a.hash_len; k++) h[k] = rec[k];
     for (uint32_t k = a.hash_len; k < 32; k++) h[k] = 0;
     const uint8_t* q = rec + a.hash_len;
-    a.p.hashloc[slot] = (uint64_t)get_be32(q) << 32 | get_be32(q + 4);
-    a.p.len[slot] = (int32_t)get_be32(q + 8);
-    a.p.pos[slot] = (int32_t)get_be32(q + 12);
-    a.p.offset[slot] = (int32_t)get_be32(q + 16);
-    a.p.nlen[slot] = (int32_t)get_be32(q + 20);
+    a.p.hashloc[slot] = (uint64_t)get_be32(q + kPairHashlocAt) << 32 | get_be32(q + kPairHashlocAt + 4);
+    a.p.len[slot] = (int32_t)get_be32(q + kPairLenAt);
+    a.p.pos[slot] = (int32_t)get_be32(q + kPairPosAt);
+    a.p.offset[slot] = (int32_t)get_be32(q + kPairOffsetAt);
+    a.p.nlen[slot] = (int32_t)get_be32(q + kPairNlenAt);
 }
 
 // one wave per buffer (every branch below is wave-uniform)
@@ -74,21 +72,20 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
     const uint32_t lane = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint8_t* img = a.map + (uint64_t)b * a.slot_bytes;
-    const uint32_t bal = a.hash_len + 24;
-    const int32_t zlen = (int32_t)get_be32(img + 5);
+    const uint32_t hl = a.hash_len;
+    const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
     uint32_t status = 0, n = 0;
     if (zlen > 0) {
-        if (13ull + (uint64_t)zlen * bal > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;  // BufferUnderflowException
+        if (slot_need((uint32_t)zlen, hl) > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;  // BufferUnderflowException
         else n = (uint32_t)zlen;
     }
-    const uint8_t* recs = img + 9;
-    const uint32_t fo = a.hash_len + 8;  // the four ints of a pair: len, pos, offset, nlen
     bool neg = false, unsorted = false;
     for (uint32_t i = lane; i < n; i += 64) {
-        const uint8_t* q = recs + (uint64_t)i * bal + fo;
-        const int32_t ps = (int32_t)get_be32(q + 4);
-        neg |= ((int32_t)get_be32(q) | ps | (int32_t)get_be32(q + 8) | (int32_t)get_be32(q + 12)) < 0;
-        if (i > 0) unsorted |= (int32_t)get_be32(q + 4 - bal) >= ps;
+        const uint8_t* q = pair_fields(img, i, hl);
+        const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
+        neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
+                (int32_t)get_be32(q + kPairNlenAt)) < 0;
+        if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hl) + kPairPosAt) >= ps;
     }
     if (wave_any(neg)) {  // HashLocPair.checkCorrupt
         status = SDFS_CDC_READ_CORRUPT;
@@ -97,10 +94,11 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
     const uint64_t base = (uint64_t)b * a.p.cap;
     uint32_t count = n;
     if (!wave_any(unsorted)) {
-        for (uint32_t i = lane; i < n; i += 64) put_pair(a, recs + (uint64_t)i * bal, base + i);
+        for (uint32_t i = lane; i < n; i += 64) put_pair(a, slot_pair(img, i, hl), base + i);
     } else {
         // TreeMap.put per pair in image order: a later pair with the same pos replaces the earlier
-        for (uint32_t i = lane; i < n; i += 64) a.tmp_pos[base + i] = (int32_t)get_be32(recs + (uint64_t)i * bal + fo + 4);
+        for (uint32_t i = lane; i < n; i += 64)
+            a.tmp_pos[base + i] = (int32_t)get_be32(pair_fields(img, i, hl) + kPairPosAt);
         __syncthreads();
         uint32_t live = 0;
         for (uint32_t i = lane; i < n; i += 64) {
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
             const int32_t ps = a.tmp_pos[base + i];
             uint32_t rank = 0;
             for (uint32_t j = 0; j < n; j++) rank += !a.tmp_dead[base + j] && a.tmp_pos[base + j] < ps;
-            put_pair(a, recs + (uint64_t)i * bal, base + rank);
+            put_pair(a, slot_pair(img, i, hl), base + rank);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o);
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
     if (lane == 0) {
         a.p.counts[b] = count;
         a.p.flags[b] = img[0];
-        a.p.doop[b] = status ? 0 : get_be32(recs + (uint64_t)n * bal);
+        a.p.doop[b] = status ? 0 : get_be32(slot_pair(img, n, hl));  // the trailer
         a.p.status[b] = status;
     }
 }
@@ -255,7 +253,7 @@ __global__ __launch_bounds__(256) void plan_remap_kernel(uint32_t* pair_fetch, u
 
 __global__ __launch_bounds__(256) void chain_lens_kernel(const uint32_t* in, const uint32_t* count, uint64_t n_max,
                                                          uint32_t* out) {
-    const uint64_t n = count ? min<uint64_t>(*count, n_max) : n_max;
+    const uint64_t n = live_count(count, n_max);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = in[i] == UINT32_MAX ? 0 : in[i];
 }
@@ -342,19 +340,6 @@ struct PairView {
     int32_t n;
 };
 
-// largest k with pos[k] <= x, -1 if none; `hint` = the answer for a nearby x
-__device__ __forceinline__ int32_t floor_pair(const PairView& v, int32_t x, int32_t hint) {
-    if (hint >= -1 && hint < v.n && (hint < 0 || v.pos[hint] <= x) && (hint + 1 >= v.n || v.pos[hint + 1] > x))
-        return hint;
-    int32_t lo = 0, hi = v.n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (v.pos[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo - 1;
-}
-
 // byte x of the buffer; k = floor entry of some x' <= x
 __device__ __forceinline__ uint8_t gather_byte(const PairView& v, const uint8_t* chunks, int32_t x, int32_t& k) {
     while (k + 1 < v.n && v.pos[k + 1] <= x) k++;
@@ -412,7 +397,7 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
         if (v >= nvec) continue;
         const int64_t o = (int64_t)v * 16 - head;  // buffer offset of the vector's first byte
         const int32_t x0 = (int32_t)max<int64_t>(o, 0);
-        k = floor_pair(pv, x0, k);
+        k = floor_index(pv.pos, pv.n, x0, k);  // the largest pos <= x0
         kf[it] = k;
         if (o < 0 || o + 16 > cl) {  // a buffer end that is not 16-byte aligned
             mode[it] = kEdge;
@@ -517,45 +502,6 @@ __global__ __launch_bounds__(64) void verify_compare_kernel(VerifyArgs a) {
 
 // ----------------------------------------------------------------------------------------- host
 
-bool pairs_complete(const sdfs_cdc_pairs* p) {
-    return p && p->counts && p->hashes && p->hashloc && p->len && p->pos && p->offset && p->nlen && p->doop &&
-           p->flags && p->status && p->cap;
-}
-
-// per-call scratch in stream order; released in the destructor (the frees are enqueued behind
-// whatever was launched on the stream before it runs)
-struct Scratch {
-    hipStream_t s;
-    void* ptrs[6] = {};
-    int n = 0;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    template <typename T>
-    hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMallocAsync(&p, std::max<size_t>(count, 1) * sizeof(T), s);
-        if (e == hipSuccess) ptrs[n++] = p;
-        *out = static_cast<T*>(p);
-        return e;
-    }
-    ~Scratch() {
-        for (int i = 0; i < n; i++) (void)hipFreeAsync(ptrs[i], s);
-    }
-};
-
-#define RD_TRY(expr)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                      \
-            return fail_status(e_ == hipErrorOutOfMemory ? SDFS_CDC_ENOMEM : SDFS_CDC_EHIP, "%s: %s", #expr, \
-                               hipGetErrorString(e_));                                             \
-    } while (0)
-
-int set_device(int device) {
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_status(SDFS_CDC_ENODEV, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-    return SDFS_CDC_OK;
-}
-
 }  // namespace
 }  // namespace sdfs
 
@@ -564,15 +510,14 @@ using namespace sdfs;
 extern "C" {
 
 uint32_t sdfs_cdc_map_pair_cap(uint32_t slot_bytes, uint32_t hash_len) {
-    return slot_bytes < 13 ? 0 : (slot_bytes - 13) / (hash_len + 24);
+    return pair_cap(slot_bytes, hash_len);
 }
 
 int sdfs_cdc_map_parse(int device, uint32_t nbuf, const uint8_t* d_map, uint32_t slot_bytes, uint32_t hash_len,
                        const sdfs_cdc_pairs* pairs, void* stream) {
     if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
-    if (hash_len != 32 && hash_len != 16)
-        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: HashLocPair holds 32 (SHA-256) or 16 (MD5) bytes", hash_len);
-    if (slot_bytes < 13) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
+    if (const int rc = check_hash_len(hash_len, HashOf::kPair)) return rc;
+    if (slot_bytes < kSlotFixedBytes) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
     if (pairs->cap < sdfs_cdc_map_pair_cap(slot_bytes, hash_len))
         return fail_status(SDFS_CDC_ECAP, "pairs.cap %u < %u pairs a %u-byte slot can hold", pairs->cap,
                            sdfs_cdc_map_pair_cap(slot_bytes, hash_len), slot_bytes);
@@ -582,10 +527,10 @@ int sdfs_cdc_map_parse(int device, uint32_t nbuf, const uint8_t* d_map, uint32_t
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc(s);
     ParseArgs a{d_map, slot_bytes, hash_len, *pairs, nullptr, nullptr};
-    RD_TRY(sc.get(&a.tmp_pos, (size_t)nbuf * pairs->cap));
-    RD_TRY(sc.get(&a.tmp_dead, (size_t)nbuf * pairs->cap));
+    SDFS_TRY(sc.get(&a.tmp_pos, (size_t)nbuf * pairs->cap));
+    SDFS_TRY(sc.get(&a.tmp_dead, (size_t)nbuf * pairs->cap));
     hipLaunchKernelGGL(map_parse_kernel, dim3(nbuf), dim3(64), 0, s, a);
-    RD_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -606,15 +551,15 @@ int sdfs_cdc_read_plan(int device, uint32_t nbuf, const sdfs_cdc_pairs* pairs, u
     Scratch sc(s);
     PlanArgs a{*pairs,    pos_base,  n_store,   d_store_off, d_store_len, d_store_raw_len, d_pair_fetch, d_fetch_count,
                d_src_off, d_src_len, d_dst_off, d_dst_cap,   d_plain_off, d_total_bytes,   nullptr};
-    RD_TRY(sc.get(&a.mark, (size_t)n_store));
-    RD_TRY(hipMemsetAsync(a.mark, 0, std::max<size_t>(n_store, 1) * 4, s));
+    SDFS_TRY(sc.get(&a.mark, (size_t)n_store));
+    SDFS_TRY(hipMemsetAsync(a.mark, 0, std::max<size_t>(n_store, 1) * 4, s));
     if (nbuf) hipLaunchKernelGGL(plan_mark_kernel, dim3(nbuf), dim3(64), 0, s, a);
     hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, a);
     const uint64_t slots = (uint64_t)nbuf * pairs->cap;
     if (slots)
         hipLaunchKernelGGL(plan_remap_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, d_pair_fetch, slots,
                            a.mark);
-    RD_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -626,7 +571,7 @@ int sdfs_cdc_read_chain_lens(int device, const uint32_t* d_in_len, const uint32_
     if (const int rc = set_device(device)) return rc;
     hipLaunchKernelGGL(chain_lens_kernel, dim3((uint32_t)((n_max + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), d_in_len, d_count, n_max, d_out_len);
-    RD_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -634,8 +579,7 @@ int sdfs_cdc_read_assemble(int device, uint32_t nbuf, uint32_t chunk_length, con
                            const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
                            const uint32_t* d_fetch_len, uint8_t* d_out, void* stream) {
     if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
-    if (chunk_length < 1 || chunk_length > (uint32_t)INT32_MAX)
-        return fail_status(SDFS_CDC_EINVAL, "chunk_length %u: 1 .. 2^31 - 1 (HashLocPair.pos is an int)", chunk_length);
+    if (const int rc = check_chunk_length(chunk_length)) return rc;
     if (nbuf && (!d_pair_fetch || !d_chunks || !d_fetch_off || !d_fetch_len || !d_out))
         return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (nbuf == 0) return SDFS_CDC_OK;
@@ -648,15 +592,15 @@ int sdfs_cdc_read_assemble(int device, uint32_t nbuf, uint32_t chunk_length, con
     AsmArgs a{*pairs, nbuf, chunk_length, d_pair_fetch, d_chunks, d_fetch_off, d_fetch_len, d_out,
               nullptr, nullptr, nullptr, nullptr, tiles};
     const size_t slots = (size_t)nbuf * pairs->cap;
-    RD_TRY(sc.get(&a.nused, nbuf));
-    RD_TRY(sc.get(&a.end, slots));
-    RD_TRY(sc.get(&a.maxend, slots));
-    RD_TRY(sc.get(&a.src, slots));
+    SDFS_TRY(sc.get(&a.nused, nbuf));
+    SDFS_TRY(sc.get(&a.end, slots));
+    SDFS_TRY(sc.get(&a.maxend, slots));
+    SDFS_TRY(sc.get(&a.src, slots));
     hipLaunchKernelGGL(assemble_status_kernel, dim3(nbuf), dim3(64), 0, s, a);
     const dim3 grid((uint32_t)((uint64_t)tiles * nbuf));
     if (pairs->cap <= kLdsPairs) hipLaunchKernelGGL(gather_kernel<true>, grid, dim3(kGatherThreads), 0, s, a);
     else hipLaunchKernelGGL(gather_kernel<false>, grid, dim3(kGatherThreads), 0, s, a);
-    RD_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -666,8 +610,7 @@ int sdfs_cdc_read_verify(sdfs_cdc_engine* engine, uint32_t nbuf, const sdfs_cdc_
                          uint8_t* d_pair_bad, uint32_t* d_bad_count, void* stream) {
     if (!engine) return fail_status(SDFS_CDC_EINVAL, "null engine");
     if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
-    if (hash_len != 32 && hash_len != 16)
-        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: HashLocPair holds 32 (SHA-256) or 16 (MD5) bytes", hash_len);
+    if (const int rc = check_hash_len(hash_len, HashOf::kPair)) return rc;
     if (nbuf && (!d_pair_fetch || !d_pair_bad || !d_bad_count)) return fail_status(SDFS_CDC_EINVAL, "null argument");
     if ((nbuf || n_fetch_max) && (!d_chunks || !d_fetch_off || !d_fetch_len))
         return fail_status(SDFS_CDC_EINVAL, "null argument");
@@ -679,24 +622,24 @@ int sdfs_cdc_read_verify(sdfs_cdc_engine* engine, uint32_t nbuf, const sdfs_cdc_
         return fail_status(SDFS_CDC_EINVAL, "engine digests are %d bytes, the pairs hold %u", dl, hash_len);
     if (nbuf == 0) return SDFS_CDC_OK;
     hipPointerAttribute_t at;
-    RD_TRY(hipPointerGetAttributes(&at, d_pair_bad));
+    SDFS_TRY(hipPointerGetAttributes(&at, d_pair_bad));
     if (const int rc = set_device(at.device)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc(s);
     uint32_t* lens = nullptr;
     uint8_t* digests = nullptr;
-    RD_TRY(sc.get(&lens, (size_t)n_fetch_max));
-    RD_TRY(sc.get(&digests, (size_t)n_fetch_max * 32));
+    SDFS_TRY(sc.get(&lens, (size_t)n_fetch_max));
+    SDFS_TRY(sc.get(&digests, (size_t)n_fetch_max * 32));
     if (n_fetch_max) {
         hipLaunchKernelGGL(chain_lens_kernel, dim3((uint32_t)((n_fetch_max + 255) / 256)), dim3(256), 0, s, d_fetch_len,
                            d_fetch_count, n_fetch_max, lens);
-        RD_TRY(hipGetLastError());
+        SDFS_TRY(hipGetLastError());
         const int rc = sdfs_cdc_hash_device(engine, d_chunks, d_fetch_off, lens, d_fetch_count, n_fetch_max, digests, stream);
         if (rc) return rc;
     }
     VerifyArgs a{*pairs, hash_len, d_pair_fetch, d_fetch_len, digests, d_pair_bad, d_bad_count};
     hipLaunchKernelGGL(verify_compare_kernel, dim3(nbuf), dim3(64), 0, s, a);
-    RD_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 

@@ -1,0 +1,165 @@
+// store_format.h — the three on-disk formats of the store layer, each defined here and nowhere
+// else (host + device).  Not part of the C-ABI.
+//
+//   slot image     SparseDataChunk.getBytes (SparseDataChunk.java:295-318, HashLocPair.asArray
+//                  HashLocPair.java:49-59); written by map_emit.hip and map_merge.hip, parsed by
+//                  read_path.hip
+//   .map image     SimpleByteArrayLongMap's file (SimpleByteArrayLongMap.java:198-261,427-498,
+//                  509-539); written by archive_pack.hip, read back by store_open.hip
+//   archive record HashBlobArchive.putChunk (HashBlobArchive.java:1399-1411); laid out and packed by
+//                  archive_pack.hip, checked by store_open.hip
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+
+#include "../../include/sdfs_archive.h"
+
+namespace sdfs {
+namespace {  // internal linkage: nothing here joins the libraries' exported symbols
+
+// ----------------------------------------------------------------------------------- byte order
+
+__device__ __forceinline__ uint32_t get_be32(const uint8_t* p) {
+    return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
+}
+
+__device__ __forceinline__ void put_be32(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24);
+    p[1] = (uint8_t)(v >> 16);
+    p[2] = (uint8_t)(v >> 8);
+    p[3] = (uint8_t)v;
+}
+
+// byte k (0 = first in memory) of put_be32(v)
+__device__ __forceinline__ uint32_t be32_byte(uint32_t v, uint32_t k) { return (v >> (8 * (3 - k))) & 255u; }
+
+// ----------------------------------------------------------------------------------- slot image
+//
+// [flags][BE32 capacity][BE32 n] n x (hash | BE64 hashloc | BE32 len, pos, offset, nlen) [BE32 doop]
+
+constexpr uint32_t kSlotHeaderBytes = 9;
+constexpr uint32_t kSlotTrailerBytes = 4;
+constexpr uint32_t kSlotFixedBytes = kSlotHeaderBytes + kSlotTrailerBytes;  // 13: an image with no pair
+constexpr uint32_t kSlotCountAt = 5;      // BE32 n (ar.size())
+// a pair's fields behind its hash
+constexpr uint32_t kPairHashlocAt = 0, kPairLenAt = 8, kPairPosAt = 12, kPairOffsetAt = 16, kPairNlenAt = 20;
+
+__host__ __device__ inline uint32_t pair_bytes(uint32_t hash_len) { return hash_len + 24; }
+
+__host__ __device__ inline uint64_t slot_need(uint32_t n, uint32_t hash_len) {
+    return (uint64_t)kSlotFixedBytes + (uint64_t)n * pair_bytes(hash_len);
+}
+
+__host__ __device__ inline uint32_t pair_cap(uint32_t slot_bytes, uint32_t hash_len) {
+    return slot_bytes < kSlotFixedBytes ? 0 : (slot_bytes - kSlotFixedBytes) / pair_bytes(hash_len);
+}
+
+// pair i of the image (read or written)
+template <typename B>
+__device__ __forceinline__ B* slot_pair(B* img, uint32_t i, uint32_t hash_len) {
+    return img + kSlotHeaderBytes + (uint64_t)i * pair_bytes(hash_len);
+}
+
+// the fields of pair i: kPair...At count from here
+template <typename B>
+__device__ __forceinline__ B* pair_fields(B* img, uint32_t i, uint32_t hash_len) {
+    return slot_pair(img, i, hash_len) + hash_len;
+}
+
+// pair i from its six fields (byte stores: records start at odd offsets)
+__device__ __forceinline__ void put_pair_record(uint8_t* img, uint32_t i, uint32_t hash_len, const uint8_t* hash,
+                                                uint64_t hashloc, uint32_t len, uint32_t pos, uint32_t offset,
+                                                uint32_t nlen) {
+    uint8_t* p = slot_pair(img, i, hash_len);
+    for (uint32_t k = 0; k < hash_len; k++) p[k] = hash[k];
+    p += hash_len;
+    put_be32(p + kPairHashlocAt, (uint32_t)(hashloc >> 32));  // hashloc = Longs.toByteArray(pos)
+    put_be32(p + kPairHashlocAt + 4, (uint32_t)hashloc);
+    put_be32(p + kPairLenAt, len);
+    put_be32(p + kPairPosAt, pos);
+    put_be32(p + kPairOffsetAt, offset);
+    put_be32(p + kPairNlenAt, nlen);
+}
+
+// header and trailer of an image of n pairs
+__device__ __forceinline__ void put_slot_frame(uint8_t* img, uint8_t flags, uint32_t n, uint32_t hash_len,
+                                               uint32_t doop) {
+    img[0] = flags;
+    put_be32(img + 1, (uint32_t)slot_need(n, hash_len));  // buf.capacity()
+    put_be32(img + kSlotCountAt, n);                      // ar.size()
+    put_be32(slot_pair(img, n, hash_len), doop);
+}
+
+// ----------------------------------------------------------------------------------- .map image
+//
+// VERSION > 0: a 16-byte header [BE32 magic][BE32 version][8 x 0]; then `size` entries of
+// hash | BE32 pos (VERSION 0) or hash | BE32 pos | BE32 len.  An entry whose hash is all zero is
+// free.  A key's home is h % size with h = map_key_hash(key); a collision walks idx - step with
+// wrap, step = 1 + h % (size - 2).
+
+constexpr uint32_t kMapHeaderBytes = 16;
+constexpr uint32_t kMapVersionAt = 4;               // BE32 version in the header
+constexpr uint32_t kMapPosAt = 0, kMapLenAt = 4;  // an entry's value fields behind its hash
+
+// NextPrime.getNextPrimeI (NextPrime.java:56-88)
+__host__ __device__ inline uint32_t map_size_rule(uint64_t sz) {
+    if (sz <= 2) return 2;
+    for (uint32_t k = 3; k < 9; k += 2)
+        if (sz <= k) return k;
+    if (sz > (uint64_t)INT32_MAX) return 0;  // the next prime would pass Integer.MAX_VALUE (itself prime)
+    if ((sz & 1) == 0) sz += 1;
+    for (uint64_t i = sz;; i += 2) {
+        bool prime = true;
+        for (uint64_t j = 3; j * j <= i; j += 2)
+            if (i % j == 0) {
+                prime = false;
+                break;
+            }
+        if (prime) return (uint32_t)i;
+    }
+}
+
+__host__ __device__ inline uint32_t map_header_bytes(uint32_t version) { return version ? kMapHeaderBytes : 0u; }
+
+__host__ __device__ inline uint32_t map_entry_bytes(uint32_t hash_len, uint32_t version) {
+    return hash_len + (version ? 8u : 4u);
+}
+
+__host__ __device__ inline uint64_t map_image_bytes(uint32_t slots, uint32_t hash_len, uint32_t version) {
+    return map_header_bytes(version) + (uint64_t)slots * map_entry_bytes(hash_len, version);
+}
+
+__device__ __forceinline__ bool map_has_magic(const uint8_t* map) {
+    return get_be32(map) == SDFS_CDC_ARCHIVE_MAP_MAGIC;
+}
+
+__device__ __forceinline__ uint32_t map_key_hash(const uint8_t* key) { return get_be32(key + 8) & 0x7fffffffu; }
+
+__device__ __forceinline__ uint32_t map_probe_home(uint32_t h, uint32_t size) { return h % size; }
+
+// size >= 3 (a map a writer fills)
+__device__ __forceinline__ uint32_t map_probe_step(uint32_t h, uint32_t size) { return 1 + h % (size - 2); }
+
+// a map of any size read back; 0 for size <= 2: such a map holds a key in its home slot only
+__device__ __forceinline__ uint32_t map_probe_step_any(uint32_t h, uint32_t size) {
+    return size > 2 ? map_probe_step(h, size) : 0;
+}
+
+__device__ __forceinline__ uint32_t map_probe_next(uint32_t idx, uint32_t step, uint32_t size) {
+    return idx >= step ? idx - step : idx + size - step;
+}
+
+// ------------------------------------------------------------------------------- archive record
+//
+// [BE32 hash_len][hash][BE32 len][record]: a record's position (layout pos, store_off) is that of
+// its first byte; the header lies before it, the length word last.  The .map value of a record is
+// the position of its length word.
+
+constexpr uint32_t kRecordLenBack = 4;  // the length word starts this far before the record's first byte
+
+__host__ __device__ inline uint32_t record_header_bytes(uint32_t hash_len) { return 8 + hash_len; }
+
+}  // namespace
+}  // namespace sdfs

@@ -19,7 +19,9 @@
 #include <cstdint>
 
 #include "../../include/sdfs_store.h"
-#include "cdc_internal.h"
+#include "block_scan.h"
+#include "call_support.h"
+#include "store_format.h"
 
 namespace sdfs {
 namespace {
@@ -28,10 +30,6 @@ constexpr uint32_t kNone = SDFS_CDC_ARCHIVE_NONE;
 constexpr uint32_t kSortLds = SDFS_CDC_STORE_SORT_LDS;
 constexpr uint32_t kEmitThreads = 1024;
 constexpr uint32_t kLensPerLaunch = 256;
-
-__device__ __forceinline__ uint32_t be32(const uint8_t* p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
 
 // 4 bytes as they lie (compared, never interpreted); p is 4-byte aligned when al4
 __device__ __forceinline__ uint32_t raw32(const uint8_t* p, bool al4) {
@@ -61,13 +59,13 @@ struct Geo {
 
 // setUp on an existing file of len bytes (len <= the row stride <= 2^31 - 1: checked on the host)
 __device__ Geo map_geometry(const uint8_t* map, uint64_t len, uint32_t hash_len, uint32_t version) {
-    Geo g{0, hash_len + 4, 0, 0};
+    Geo g{0, map_entry_bytes(hash_len, 0), 0, 0};
     if (version != 0) {
-        if (len <= 16) return g;  // a new map: no entries
-        if (be32(map) == SDFS_CDC_ARCHIVE_MAP_MAGIC) {
-            g.off = 16;
-            g.el = hash_len + 8;
-            g.ver = be32(map + 4);
+        if (len <= kMapHeaderBytes) return g;  // a new map: no entries
+        if (map_has_magic(map)) {
+            g.off = kMapHeaderBytes;
+            g.el = map_entry_bytes(hash_len, 1);
+            g.ver = get_be32(map + kMapVersionAt);
         }
     }
     g.size = (uint32_t)((len - g.off) / g.el);  // trailing bytes are ignored
@@ -94,16 +92,16 @@ struct Rec {
 // from img before its offset is known to lie inside [header_bytes, ab).
 __device__ Rec check_record(const Img& im, const Geo& g, const uint8_t* slot, const uint8_t* img, uint64_t ab) {
     const uint32_t hl = im.hash_len;
-    const uint32_t v = be32(slot + hl);
-    const uint64_t p = (uint64_t)v + 4;  // the record's first byte
-    Rec r{v + 4, 0, 0};
+    const uint32_t v = get_be32(slot + hl + kMapPosAt);  // the map value: where the length word lies
+    const uint64_t p = (uint64_t)v + kRecordLenBack;  // the record's first byte
+    Rec r{v + kRecordLenBack, 0, 0};
     // the record's header [BE32 hl][key][BE32 len] starts at or after header_bytes, its length word ends by ab
-    if (p < (uint64_t)im.header_bytes + 8 + hl || p > ab || p > (uint64_t)UINT32_MAX) {
+    if (p < (uint64_t)im.header_bytes + record_header_bytes(hl) || p > ab || p > (uint64_t)UINT32_MAX) {
         r.flags = SDFS_CDC_STORE_RANGE;
         return r;
     }
-    const uint32_t img_len = be32(img + p - 4);
-    const uint32_t len = g.ver > 0 ? be32(slot + hl + 4) : img_len;
+    const uint32_t img_len = get_be32(img + p - kRecordLenBack);
+    const uint32_t len = g.ver > 0 ? get_be32(slot + hl + kMapLenAt) : img_len;
     if (p + len > ab) {
         r.flags = SDFS_CDC_STORE_RANGE;
         return r;
@@ -113,8 +111,8 @@ __device__ Rec check_record(const Img& im, const Geo& g, const uint8_t* slot, co
         r.flags |= SDFS_CDC_STORE_LEN;
         r.len = 0;
     }
-    const uint8_t* h = img + p - 8 - hl;
-    uint32_t diff = be32(h) ^ hl;
+    const uint8_t* h = img + p - record_header_bytes(hl);
+    uint32_t diff = get_be32(h) ^ hl;
     for (uint32_t i = 0; i < hl; i++) diff |= (uint32_t)(h[4 + i] ^ slot[i]);
     if (diff) r.flags |= SDFS_CDC_STORE_KEY;
     return r;
@@ -126,7 +124,7 @@ __device__ __forceinline__ uint32_t nz_rule(const uint8_t* rec, uint32_t len, ui
         flags |= SDFS_CDC_STORE_NZ;
         return 0;
     }
-    const int32_t nz = (int32_t)be32(rec);
+    const int32_t nz = (int32_t)get_be32(rec);
     const uint32_t raw = nz > 0 ? (uint32_t)nz : len - 4;
     if (raw > max_chunk) {
         flags |= SDFS_CDC_STORE_NZ;
@@ -178,18 +176,11 @@ __global__ __launch_bounds__(256) void store_count_kernel(ScanArgs2 a) {
 __global__ __launch_bounds__(1024) void store_prefix_kernel(ScanArgs2 a) {
     __shared__ uint64_t part[1024];
     const uint32_t t = threadIdx.x, n = a.im.n_arc;
-    const uint32_t per = (n + 1023) / 1024;
-    const uint32_t a0 = min(t * per, n), a1 = min(a0 + per, n);
+    uint32_t a0, a1;
+    block_run_1024(n, a0, a1);
     uint64_t sum = 0;
     for (uint32_t i = a0; i < a1; i++) sum += a.cnt[i];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        const uint64_t v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
+    const uint64_t incl = block_inclusive_scan_1024(sum, part);
     const uint64_t total = part[1023];
     const bool fits = total <= a.r.n_cap;
     if (t == 0) {
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(1024) void store_prefix_kernel(ScanArgs2 a) {
         *a.r.status = fits ? 0 : SDFS_CDC_STORE_ECAP;
     }
     if (!fits) return;
-    uint64_t run = part[t] - sum;
+    uint64_t run = incl - sum;
     for (uint32_t i = a0; i < a1; i++) {
         a.o.arc_first[i] = (uint32_t)run;
         run += a.cnt[i];
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(kEmitThreads) void store_emit_kernel(ScanArgs2 a) {
             if (!slot_free(slot, hl, a.im.al4)) {
                 const uint32_t at = atomicAdd(&s_n, 1u);
                 filled = at < cnt;  // always, unless the image changed under the scan
-                if (filled) keys[at] = ((uint64_t)(be32(slot + hl) + 4) << 32) | s;
+                if (filled) keys[at] = ((uint64_t)(get_be32(slot + hl + kMapPosAt) + kRecordLenBack) << 32) | s;
             }
         }
         if (s < a.o.slot_stride && !filled) srow[s] = kNone;
@@ -279,7 +270,7 @@ __global__ __launch_bounds__(kEmitThreads) void store_emit_kernel(ScanArgs2 a) {
             if (a.plain) raw = nz_rule(img + rec.pos, rec.len, a.max_chunk, rec.flags);
             else if (rec.len < 4) rec.flags |= SDFS_CDC_STORE_NZ;
         }
-        if (rec.flags == 0) sum += 8ull + hl + rec.len;
+        if (rec.flags == 0) sum += (uint64_t)record_header_bytes(hl) + rec.len;
         const uint64_t r = (uint64_t)first + i;  // < n_cap: the prefix kernel saw the total fit
         a.r.arc[r] = arc;
         a.r.slot[r] = s;
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(256) void store_raw_lens_kernel(const uint8_t* plai
                                                              const uint32_t* len, const uint32_t* count,
                                                              uint64_t n_max, uint32_t max_chunk, uint32_t* raw_len,
                                                              uint32_t* flags) {
-    const uint64_t n = count ? min<uint64_t>(*count, n_max) : n_max;
+    const uint64_t n = live_count(count, n_max);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     uint32_t f = flags[i], raw = 0;
@@ -350,7 +341,7 @@ __device__ __forceinline__ uint64_t dir_entry(const DirArgs& a, uint64_t r, int&
 }
 
 __global__ __launch_bounds__(256) void store_dir_claim_kernel(DirArgs a) {
-    const uint64_t n = a.count ? min<uint64_t>(*a.count, a.n_max) : a.n_max;
+    const uint64_t n = live_count(a.count, a.n_max);
     const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
     int why = 0;
@@ -360,7 +351,7 @@ __global__ __launch_bounds__(256) void store_dir_claim_kernel(DirArgs a) {
 }
 
 __global__ __launch_bounds__(256) void store_dir_write_kernel(DirArgs a) {
-    const uint64_t n = a.count ? min<uint64_t>(*a.count, a.n_max) : a.n_max;
+    const uint64_t n = live_count(a.count, a.n_max);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < a.n_store) {
         const uint32_t r = a.owner[i];
@@ -408,9 +399,9 @@ __global__ __launch_bounds__(256) void store_lookup_kernel(LookArgs a) {
         const uint8_t* map = a.im.maps + (uint64_t)arc * a.im.map_stride;
         const Geo g = map_geometry(map, a.im.map_len[arc], hl, a.im.version);
         if (g.size) {
-            const uint32_t h = be32(key + 8) & 0x7fffffffu;
-            const uint32_t home = h % g.size;
-            const uint32_t step = g.size > 2 ? 1 + h % (g.size - 2) : 0;  // size <= 2: the home slot only
+            const uint32_t h = map_key_hash(key);
+            const uint32_t home = map_probe_home(h, g.size);
+            const uint32_t step = map_probe_step_any(h, g.size);  // 0 for size <= 2: the home slot only
             uint32_t idx = home;
             for (uint32_t tries = 0; tries < g.size; tries++) {  // every slot lies below map_len: size = (len - off) / el
                 const uint8_t* slot = map + g.off + (uint64_t)idx * g.el;
@@ -434,7 +425,7 @@ __global__ __launch_bounds__(256) void store_lookup_kernel(LookArgs a) {
                     break;
                 }
                 if (!filled || !step) break;  // FREE: absent
-                idx = idx >= step ? idx - step : idx + g.size - step;
+                idx = map_probe_next(idx, step, g.size);
                 if (idx == home) break;
             }
         }
@@ -450,7 +441,7 @@ __global__ __launch_bounds__(256) void store_lookup_kernel(LookArgs a) {
 
 __global__ __launch_bounds__(256) void store_verify_lens_kernel(const uint32_t* len, const uint32_t* flags,
                                                                 const uint32_t* count, uint64_t n_max, uint32_t* out) {
-    const uint64_t n = count ? min<uint64_t>(*count, n_max) : n_max;
+    const uint64_t n = live_count(count, n_max);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = (len[i] == UINT32_MAX || (flags[i] & SDFS_CDC_STORE_UNREADABLE)) ? 0 : len[i];
 }
@@ -458,7 +449,7 @@ __global__ __launch_bounds__(256) void store_verify_lens_kernel(const uint32_t* 
 __global__ __launch_bounds__(256) void store_verify_compare_kernel(const uint32_t* len, const uint8_t* keys,
                                                                    const uint8_t* digests, const uint32_t* count,
                                                                    uint64_t n_max, uint32_t hash_len, uint32_t* flags) {
-    const uint64_t n = count ? min<uint64_t>(*count, n_max) : n_max;
+    const uint64_t n = live_count(count, n_max);
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint32_t f = flags[i];
@@ -474,49 +465,12 @@ __global__ __launch_bounds__(256) void store_verify_compare_kernel(const uint32_
 
 // ----------------------------------------------------------------------------------------- host
 
-struct Scratch {
-    hipStream_t s;
-    void* ptrs[6] = {};
-    int n = 0;
-    explicit Scratch(hipStream_t st) : s(st) {}
-    template <typename T>
-    hipError_t get(T** out, size_t count) {
-        void* p = nullptr;
-        const hipError_t e = hipMallocAsync(&p, std::max<size_t>(count, 1) * sizeof(T), s);
-        if (e == hipSuccess) ptrs[n++] = p;
-        *out = static_cast<T*>(p);
-        return e;
-    }
-    ~Scratch() {
-        for (int i = 0; i < n; i++) (void)hipFreeAsync(ptrs[i], s);
-    }
-};
-
-#define ST_TRY(expr)                                                                               \
-    do {                                                                                           \
-        const hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess)                                                                      \
-            return fail_status(e_ == hipErrorOutOfMemory ? SDFS_CDC_ENOMEM : SDFS_CDC_EHIP, "%s: %s", #expr, \
-                               hipGetErrorString(e_));                                             \
-    } while (0)
-
-int set_device(int device) {
-    const hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail_status(SDFS_CDC_ENODEV, "hipSetDevice(%d): %s", device, hipGetErrorString(e));
-    return SDFS_CDC_OK;
-}
-
 // the checks the scan and the lookup share; 0 = fine
 int check_images(uint32_t n_arc, const uint8_t* d_store, const uint64_t* d_arc_base, const uint64_t* d_arc_bytes,
                  const uint8_t* d_maps, uint64_t map_stride_bytes, const uint64_t* map_len, uint32_t hash_len,
                  uint32_t header_bytes) {
-    if (hash_len == 20)
-        return fail_status(SDFS_CDC_EINVAL,
-                           "hash_len 20: the reference's map slots are made for hashLength 18 and do not hold the key");
-    if (hash_len != 16 && hash_len != 32)
-        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: 16 (MD5) or 32 (SHA-256)", hash_len);
-    if (header_bytes != 0 && header_bytes != SDFS_CDC_ARCHIVE_HEADER)
-        return fail_status(SDFS_CDC_EINVAL, "header_bytes %u: 0 (VERSION 0) or %u", header_bytes, SDFS_CDC_ARCHIVE_HEADER);
+    if (const int rc = check_hash_len(hash_len, HashOf::kMapKey)) return rc;
+    if (const int rc = check_header(header_bytes)) return rc;
     if (n_arc && (!d_store || !d_arc_base || !d_arc_bytes || !d_maps || !map_len))
         return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (map_stride_bytes > (uint64_t)INT32_MAX)
@@ -579,8 +533,8 @@ int sdfs_cdc_store_scan(int device, uint32_t n_arc, const uint8_t* d_store, uint
     Scratch sc(s);
     ScanArgs2 a{};
     uint64_t* d_len = nullptr;
-    ST_TRY(sc.get(&d_len, n_arc));
-    ST_TRY(sc.get(&a.cnt, n_arc));
+    SDFS_TRY(sc.get(&d_len, n_arc));
+    SDFS_TRY(sc.get(&a.cnt, n_arc));
     a.im = make_img(n_arc, d_store, store_bytes, d_arc_base, d_arc_bytes, d_maps, map_stride_bytes, d_len, hash_len,
                     version, header_bytes);
     a.r = *recs;
@@ -591,16 +545,16 @@ int sdfs_cdc_store_scan(int device, uint32_t n_arc, const uint8_t* d_store, uint
     if (!lds && n_arc) {
         a.sort_stride = 1;
         while (a.sort_stride < arcs->slot_stride) a.sort_stride <<= 1;
-        ST_TRY(sc.get(&a.sort, (size_t)a.sort_stride * n_arc));
+        SDFS_TRY(sc.get(&a.sort, (size_t)a.sort_stride * n_arc));
     }
-    ST_TRY(upload_lens(map_len, n_arc, d_len, s));
+    SDFS_TRY(upload_lens(map_len, n_arc, d_len, s));
     if (n_arc) hipLaunchKernelGGL(store_count_kernel, dim3(n_arc), dim3(256), 0, s, a);
     hipLaunchKernelGGL(store_prefix_kernel, dim3(1), dim3(1024), 0, s, a);
     if (n_arc) {
         if (lds) hipLaunchKernelGGL(store_emit_kernel<true>, dim3(n_arc), dim3(kEmitThreads), 0, s, a);
         else hipLaunchKernelGGL(store_emit_kernel<false>, dim3(n_arc), dim3(kEmitThreads), 0, s, a);
     }
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -617,7 +571,7 @@ int sdfs_cdc_store_raw_lens(int device, const uint8_t* d_plain, const uint64_t* 
     hipLaunchKernelGGL(store_raw_lens_kernel, dim3((uint32_t)((n_max + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), d_plain, d_off, d_len, d_count, n_max, max_chunk, d_raw_len,
                        d_flags);
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -641,13 +595,13 @@ int sdfs_cdc_store_directory(int device, const uint64_t* d_rec_store_off, const 
     Scratch sc(s);
     DirArgs a{d_rec_store_off, d_rec_len,   d_rec_raw_len, d_rec_flags,     d_hashloc,  d_count, n_max,  pos_base,
               n_store,         d_store_off, d_store_len,   d_store_raw_len, d_rec_of_k, d_info,  nullptr};
-    ST_TRY(sc.get(&a.owner, (size_t)n_store));
-    ST_TRY(hipMemsetAsync(a.owner, 0xFF, std::max<size_t>(n_store, 1) * 4, s));
-    ST_TRY(hipMemsetAsync(d_info, 0, 24, s));
+    SDFS_TRY(sc.get(&a.owner, (size_t)n_store));
+    SDFS_TRY(hipMemsetAsync(a.owner, 0xFF, std::max<size_t>(n_store, 1) * 4, s));
+    SDFS_TRY(hipMemsetAsync(d_info, 0, 24, s));
     if (n_max) hipLaunchKernelGGL(store_dir_claim_kernel, dim3((uint32_t)((n_max + 255) / 256)), dim3(256), 0, s, a);
     const uint64_t m = std::max(n_max, n_store);
     if (m) hipLaunchKernelGGL(store_dir_write_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, s, a);
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -668,13 +622,13 @@ int sdfs_cdc_store_lookup(int device, uint32_t n_arc, const uint8_t* d_store, ui
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc(s);
     uint64_t* d_len_map = nullptr;
-    ST_TRY(sc.get(&d_len_map, n_arc));
-    ST_TRY(upload_lens(map_len, n_arc, d_len_map, s));
+    SDFS_TRY(sc.get(&d_len_map, n_arc));
+    SDFS_TRY(upload_lens(map_len, n_arc, d_len_map, s));
     LookArgs a{make_img(n_arc, d_store, store_bytes, d_arc_base, d_arc_bytes, d_maps, map_stride_bytes, d_len_map,
                         hash_len, version, header_bytes),
                d_q_arc, d_q_key, n_q, d_slot, d_pos, d_len, d_store_off, d_flags};
     hipLaunchKernelGGL(store_lookup_kernel, dim3((uint32_t)((n_q + 255) / 256)), dim3(256), 0, s, a);
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 
@@ -682,11 +636,7 @@ int sdfs_cdc_store_verify(sdfs_cdc_engine* engine, const uint8_t* d_chunks, cons
                           const uint32_t* d_len, const uint8_t* d_keys, const uint32_t* d_count, uint64_t n_max,
                           uint32_t hash_len, uint32_t* d_flags, void* stream) {
     if (!engine) return fail_status(SDFS_CDC_EINVAL, "null engine");
-    if (hash_len == 20)
-        return fail_status(SDFS_CDC_EINVAL,
-                           "hash_len 20: the reference's map slots are made for hashLength 18 and do not hold the key");
-    if (hash_len != 16 && hash_len != 32)
-        return fail_status(SDFS_CDC_EINVAL, "hash_len %u: 16 (MD5) or 32 (SHA-256)", hash_len);
+    if (const int rc = check_hash_len(hash_len, HashOf::kMapKey)) return rc;
     if (n_max && (!d_chunks || !d_off || !d_len || !d_keys || !d_flags))
         return fail_status(SDFS_CDC_EINVAL, "null argument");
     if (n_max >= (uint64_t)UINT32_MAX)
@@ -697,21 +647,21 @@ int sdfs_cdc_store_verify(sdfs_cdc_engine* engine, const uint8_t* d_chunks, cons
         return fail_status(SDFS_CDC_EINVAL, "engine digests are %d bytes, the keys hold %u", dl, hash_len);
     if (n_max == 0) return SDFS_CDC_OK;
     hipPointerAttribute_t at;
-    ST_TRY(hipPointerGetAttributes(&at, d_flags));
+    SDFS_TRY(hipPointerGetAttributes(&at, d_flags));
     if (const int rc = set_device(at.device)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc(s);
     uint32_t* lens = nullptr;
     uint8_t* digests = nullptr;
-    ST_TRY(sc.get(&lens, (size_t)n_max));
-    ST_TRY(sc.get(&digests, (size_t)n_max * 32));
+    SDFS_TRY(sc.get(&lens, (size_t)n_max));
+    SDFS_TRY(sc.get(&digests, (size_t)n_max * 32));
     const dim3 grid((uint32_t)((n_max + 255) / 256));
     hipLaunchKernelGGL(store_verify_lens_kernel, grid, dim3(256), 0, s, d_len, d_flags, d_count, n_max, lens);
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     if (const int rc = sdfs_cdc_hash_device(engine, d_chunks, d_off, lens, d_count, n_max, digests, stream)) return rc;
     hipLaunchKernelGGL(store_verify_compare_kernel, grid, dim3(256), 0, s, d_len, d_keys, digests, d_count, n_max,
                        hash_len, d_flags);
-    ST_TRY(hipGetLastError());
+    SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
 

@@ -18,8 +18,8 @@ from dataclasses import dataclass, field
 
 from . import _lib
 from ._lib import (EXT_BAD_INSERT, EXT_CORRUPT, EXT_ECAP, EXT_HOLE, EXT_OVERFLOW, EXT_OVERLAP, EXT_SRC,  # noqa: F401
-                   check)
-from .read import ParsedPairs, _stream, pair_cap, parse_map_slots
+                   check, ptr, stream_of)
+from .read import ParsedPairs, pair_cap, parse_map_slots
 
 
 def split_extent(sstart: int, dstart: int, length: int, chunk_length: int):
@@ -120,8 +120,8 @@ def map_extents(src: ParsedPairs, segments, nbuf_dst: int, chunk_length: int, n_
     status = torch.zeros(max(n_seg, 1), dtype=torch.int32, device=dev)
     d = _upload(h, dev)
     check(_lib.load().sdfs_cdc_map_extents(int(device), src.nbuf, ctypes.byref(src.c), int(nbuf_dst), int(chunk_length),
-                                           n_seg, h.ctypes.data, d.data_ptr(), ctypes.byref(ins.c),
-                                           int(n_ins_cap), first.data_ptr(), status.data_ptr(), _stream(first, stream)))
+                                           n_seg, h.ctypes.data, d.data_ptr(), ctypes.byref(ins.c), int(n_ins_cap),
+                                           first.data_ptr(), status.data_ptr(), stream_of(first, stream)))
     return ins, first, status[:n_seg]
 
 
@@ -146,7 +146,7 @@ def inserts_from_chunks(batch, hashloc, dst_buf, run_pos, nbuf_dst: int, chunk_l
     check(_lib.load().sdfs_cdc_map_inserts_from_chunks(
         int(device), batch.nbuf, ctypes.byref(batch.out), batch.buf_len, hashloc.data_ptr(), int(nbuf_dst),
         int(chunk_length), h.ctypes.data, d.data_ptr(), ctypes.byref(ins.c), int(n_ins_cap), first.data_ptr(),
-        _stream(first, stream)))
+        stream_of(first, stream)))
     return ins, first
 
 
@@ -177,7 +177,7 @@ def insert_pairs(pairs: ParsedPairs, ins: InsertList, ins_first, chunk_length: i
     check(_lib.load().sdfs_cdc_map_insert(int(device), pairs.nbuf, int(chunk_length), int(slot_pairs),
                                           ctypes.byref(pairs.c), ctypes.byref(ins.c), int(ins.cap),
                                           ins_first.data_ptr(), ctypes.byref(out.c), dup.data_ptr(), status.data_ptr(),
-                                          _stream(status, stream)))
+                                          stream_of(status, stream)))
     return out, dup, status[: pairs.nbuf]
 
 
@@ -193,10 +193,9 @@ def emit_pairs(pairs: ParsedPairs, m, slot_len: int, dup=None, status=None, flag
     doop = torch.zeros(max(pairs.nbuf, 1), dtype=torch.int32, device=dev)
     skipped = torch.zeros(1, dtype=torch.int32, device=dev)
     check(_lib.load().sdfs_cdc_map_emit_pairs(int(device), pairs.nbuf, ctypes.byref(pairs.c), pairs.hash_len,
-                                              dup.data_ptr() if dup is not None else None,
-                                              status.data_ptr() if status is not None else None, int(flags),
+                                              ptr(dup), ptr(status), int(flags),
                                               m.data_ptr(), int(slot_len), doop.data_ptr(), skipped.data_ptr(),
-                                              _stream(m, stream)))
+                                              stream_of(m, stream)))
     return doop[: pairs.nbuf], skipped
 
 

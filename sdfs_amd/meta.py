@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from ._lib import check
+from ._lib import check, stream_of
 
 
 def slot_bytes(hash_len: int, chunk_length: int, min_len: int) -> int:
@@ -33,7 +33,7 @@ def emit_map_slots(batch, dup, hashloc, hash_len: int = 32, slot_len: int | None
     m = torch.zeros(batch.nbuf * slot_len, dtype=torch.uint8, device=dev)
     doop = torch.zeros(batch.nbuf, dtype=torch.int32, device=dev)
     ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     check(lib.sdfs_cdc_map_emit(int(device), batch.nbuf, ctypes.byref(batch.out), int(hash_len), dup.data_ptr(),
-                                hashloc.data_ptr(), m.data_ptr(), slot_len, doop.data_ptr(), ovf.data_ptr(), s))
+                                hashloc.data_ptr(), m.data_ptr(), slot_len, doop.data_ptr(), ovf.data_ptr(),
+                                stream_of(m, stream)))
     return m, doop, ovf

@@ -20,7 +20,7 @@ import ctypes
 from dataclasses import dataclass
 
 from . import _lib
-from ._lib import READ_BOUNDS, READ_CORRUPT, READ_FETCH, READ_MISSING, READ_NONE, check  # noqa: F401
+from ._lib import READ_BOUNDS, READ_CORRUPT, READ_FETCH, READ_MISSING, READ_NONE, check, ptr, stream_of  # noqa: F401
 
 
 def pair_cap(slot_len: int, hash_len: int = 32) -> int:
@@ -54,12 +54,6 @@ class ParsedPairs:
             status=self.status.data_ptr(), cap=self.cap, reserved=0)
 
 
-def _stream(t, stream):
-    import torch
-
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-
-
 def parse_map_slots(m, nbuf: int, slot_len: int, hash_len: int = 32, device: int = 0, stream=None) -> ParsedPairs:
     """m: device uint8 tensor holding nbuf slots of slot_len bytes (``emit_map_slots``' output)."""
     import torch
@@ -75,7 +69,7 @@ def parse_map_slots(m, nbuf: int, slot_len: int, hash_len: int = 32, device: int
     if m.numel() < nbuf * slot_len:
         raise ValueError(f"map holds {m.numel()} bytes, {nbuf} slots of {slot_len} need {nbuf * slot_len}")
     check(_lib.load().sdfs_cdc_map_parse(int(device), int(nbuf), m.data_ptr(), int(slot_len), int(hash_len),
-                                         ctypes.byref(pairs.c), _stream(m, stream)))
+                                         ctypes.byref(pairs.c), stream_of(m, stream)))
     return pairs
 
 
@@ -98,7 +92,7 @@ def plan_reads(pairs: ParsedPairs, store_off, store_len, store_raw_len, pos_base
         store_len.data_ptr() if n else None, store_raw_len.data_ptr() if n else None, out["pair_fetch"].data_ptr(),
         out["fetch_count"].data_ptr(), out["src_off"].data_ptr(), out["src_len"].data_ptr(),
         out["dst_off"].data_ptr(), out["dst_cap"].data_ptr(), out["plain_off"].data_ptr(),
-        out["total_bytes"].data_ptr(), _stream(pairs.counts, stream)))
+        out["total_bytes"].data_ptr(), stream_of(pairs.counts, stream)))
     return out
 
 
@@ -108,8 +102,8 @@ def chain_lens(in_len, count=None, device: int = 0, stream=None):
 
     out = torch.empty_like(in_len)
     check(_lib.load().sdfs_cdc_read_chain_lens(int(device), in_len.data_ptr(),
-                                               count.data_ptr() if count is not None else None,
-                                               int(in_len.shape[0]), out.data_ptr(), _stream(in_len, stream)))
+                                               ptr(count), int(in_len.shape[0]), out.data_ptr(),
+                                               stream_of(in_len, stream)))
     return out
 
 
@@ -122,7 +116,7 @@ def assemble(pairs: ParsedPairs, chunk_length: int, pair_fetch, chunks, fetch_of
         out = torch.empty((pairs.nbuf, chunk_length), dtype=torch.uint8, device=chunks.device)
     check(_lib.load().sdfs_cdc_read_assemble(int(device), pairs.nbuf, int(chunk_length), ctypes.byref(pairs.c),
                                              pair_fetch.data_ptr(), chunks.data_ptr(), fetch_off.data_ptr(),
-                                             fetch_len.data_ptr(), out.data_ptr(), _stream(chunks, stream)))
+                                             fetch_len.data_ptr(), out.data_ptr(), stream_of(chunks, stream)))
     return out
 
 
@@ -136,7 +130,7 @@ def verify_reads(engine, pairs: ParsedPairs, pair_fetch, chunks, fetch_off, fetc
     check(_lib.load().sdfs_cdc_read_verify(engine._h, pairs.nbuf, ctypes.byref(pairs.c), pairs.hash_len,
                                            pair_fetch.data_ptr(), chunks.data_ptr(), fetch_off.data_ptr(),
                                            fetch_len.data_ptr(), fetch_count.data_ptr(), int(fetch_len.shape[0]),
-                                           bad.data_ptr(), cnt.data_ptr(), _stream(chunks, stream)))
+                                           bad.data_ptr(), cnt.data_ptr(), stream_of(chunks, stream)))
     return bad, cnt
 
 

@@ -22,14 +22,8 @@ from dataclasses import dataclass
 
 from . import _lib
 from ._lib import (ARCHIVE_HEADER, STORE_ECAP, STORE_FETCH, STORE_GAP, STORE_HASH, STORE_KEY, STORE_LEN,  # noqa: F401
-                   STORE_NZ, STORE_RANGE, STORE_SLOTS, STORE_UNREADABLE, check)
+                   STORE_NZ, STORE_RANGE, STORE_SLOTS, STORE_UNREADABLE, check, ptr, stream_of)
 from .archive import ArchiveSet, Layout, _r16, map_bytes
-
-
-def _stream(t, stream):
-    import torch
-
-    return stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _host_lens(map_len):
@@ -119,7 +113,7 @@ def scan_store(store, arc_base, arc_bytes, maps, map_len, hash_len: int = 32, ve
     check(_lib.load().sdfs_cdc_store_scan(
         int(device), n_arc, store.data_ptr(), int(store.numel()), arc_base.data_ptr(), arc_bytes.data_ptr(),
         maps.data_ptr(), stride, c_lens, hl, int(version), header, int(max_chunk), int(bool(plain)),
-        ctypes.byref(recs), ctypes.byref(arcs), _stream(store, stream)))
+        ctypes.byref(recs), ctypes.byref(arcs), stream_of(store, stream)))
     return sc
 
 
@@ -131,8 +125,8 @@ def raw_lens(plain, off, length, flags, max_chunk: int = 32768, count=None, devi
     n = int(length.shape[0])
     out = torch.empty(max(n, 1), dtype=torch.int32, device=plain.device)[:n]
     check(_lib.load().sdfs_cdc_store_raw_lens(int(device), plain.data_ptr(), off.data_ptr(), length.data_ptr(),
-                                              count.data_ptr() if count is not None else None, n, int(max_chunk),
-                                              out.data_ptr(), flags.data_ptr(), _stream(plain, stream)))
+                                              ptr(count), n, int(max_chunk),
+                                              out.data_ptr(), flags.data_ptr(), stream_of(plain, stream)))
     return out
 
 
@@ -150,8 +144,8 @@ def directory(store_off, length, raw_len, flags, hashloc, pos_base: int, n_store
     p = lambda t: t.data_ptr() if k else None  # noqa: E731
     check(_lib.load().sdfs_cdc_store_directory(
         int(device), store_off.data_ptr(), length.data_ptr(), raw_len.data_ptr(), flags.data_ptr(), hashloc.data_ptr(),
-        count.data_ptr() if count is not None else None, n, int(pos_base), k, p(o_off), p(o_len), p(o_raw), p(o_rec),
-        info.data_ptr(), _stream(hashloc, stream)))
+        ptr(count), n, int(pos_base), k, p(o_off), p(o_len), p(o_raw), p(o_rec),
+        info.data_ptr(), stream_of(hashloc, stream)))
     return o_off, o_len, o_raw, o_rec.to(torch.int64), info
 
 
@@ -268,7 +262,7 @@ def lookup(arcs: ArchiveSet, arc, keys, device: int = 0, stream=None) -> Lookup:
         int(device), n_arc, arcs.store.data_ptr(), int(arcs.store.numel()), ab.data_ptr(), bb.data_ptr(),
         arcs.maps.data_ptr(), stride, c_lens, arcs.hash_len, arcs.version, arcs.header_bytes, arc.data_ptr(),
         keys.data_ptr(), n, out.slot.data_ptr(), out.pos.data_ptr(), out.len.data_ptr(), out.store_off.data_ptr(),
-        out.flags.data_ptr(), _stream(arcs.store, stream)))
+        out.flags.data_ptr(), stream_of(arcs.store, stream)))
     return out
 
 
@@ -276,8 +270,8 @@ def verify(engine, chunks, off, length, keys, flags, hash_len: int = 32, count=N
     """``sdfs_cdc_store_verify``: STORE_FETCH / STORE_HASH or-ed into ``flags`` (int32 [n], in place)."""
     n = int(length.shape[0])
     check(_lib.load().sdfs_cdc_store_verify(engine._h, chunks.data_ptr(), off.data_ptr(), length.data_ptr(),
-                                            keys.data_ptr(), count.data_ptr() if count is not None else None, n,
-                                            int(hash_len), flags.data_ptr(), _stream(chunks, stream)))
+                                            keys.data_ptr(), ptr(count), n,
+                                            int(hash_len), flags.data_ptr(), stream_of(chunks, stream)))
 
 
 def scrub(arcs: ArchiveSet, engine, aes=None, batch_records: int = 65536, device: int = 0, stages=None):

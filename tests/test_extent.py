@@ -571,6 +571,53 @@ def test_gpu_map_extents_vs_get_wl():
         assert grows[gfirst[b]:gfirst[b + 1]] == by_buf[b], b
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_seg", [1023, 1025, 2049])
+def test_gpu_map_extents_many_segments(n_seg):
+    """seg_first is a one-block prefix over the segments' piece counts: 1 023 leaves its last
+    thread without a segment, 1 025 and 2 049 give a thread more than one and are no multiple of
+    the block.  Short segments over two source buffers, some of them ending in a hole (no
+    pieces); seg_first (all n_seg + 1 entries), seg_status and the pieces against the model."""
+    import torch
+
+    from sdfs_amd.extent import map_extents
+    from sdfs_amd.read import parse_map_slots
+
+    cl, slot_len = 4096, 13 + 56 * 24
+    src = [[bp(20 + i, 64 * i, 64, offset=i) for i in range(20)],       # 0 .. 1280 tiled
+           [bp(60 + i, 55 * i, 55, offset=2 * i) for i in range(20)]]  # 0 .. 1100 tiled
+    # (src_buf, src_off, dst_buf, dst_off, len): 1 .. 70 bytes, so one to three pieces each
+    segs = [(s % 2, (s * 37) % 1200, s % 3, (s * 11) % 4000, 1 + s % 70) for s in range(n_seg)]
+    m = _slots([R.build_image([p[:6] for p in b]) for b in src], slot_len)
+    p = parse_map_slots(m, 2, slot_len, 32)
+    ins, first, status = map_extents(p, segs, 3, cl, n_ins_cap=3 * n_seg)
+    torch.cuda.synchronize()
+    first, status = first.cpu().numpy(), status.cpu().numpy()
+    rows = list(zip(ins.hash.cpu().numpy(), ins.hashloc.tolist(), ins.len.tolist(), ins.pos.tolist(),
+                    ins.offset.tolist(), ins.nlen.tolist(), ins.dst_buf.tolist()))
+    trees = [X.tree(b) for b in src]
+    want_first, want_status, want = [0], [], []
+    for sb, so, db, do, ln in segs:
+        pieces, st, x = [], 0, so
+        try:
+            while x < so + ln:
+                w = X.get_wl(trees[sb], x)
+                k = min(w[X.NLEN], so + ln - x)
+                pieces.append((w[X.HASH], w[X.HASHLOC], w[X.LEN], do + x - so, w[X.OFFSET], k, db))
+                x += k
+        except X.NotFound:
+            pieces, st = [], _lib.EXT_HOLE
+        want += pieces
+        want_status.append(st)
+        want_first.append(len(want))
+    assert want_status.count(_lib.EXT_HOLE) >= 50 and len(want) > n_seg  # both kinds occur
+    assert first.tolist() == want_first
+    assert status.tolist() == want_status
+    got = [(h.tobytes(),) + tuple(r) for h, *r in rows[:len(want)]]
+    assert got == want
+    assert all(r[6] == 3 for r in rows[len(want):])  # rows past the total keep the fill
+
+
 # ---- end to end: the writer's store, copies and rewrites, the reader, the index
 
 _KEY = bytes(range(7, 39))

@@ -49,18 +49,19 @@ def _host_images(counts, st, ln, dg, dup, loc, hash_len):
     return out
 
 
-def _run(engine, nbuf, hash_len, slot_len=None, holes=True):
+def _run(engine, nbuf, hash_len, slot_len=None, holes=True, buf_len=262144):
     import torch
 
     from sdfs_amd.device import DeviceBatch
     from sdfs_amd.index import HipHashesMap
     from sdfs_amd.meta import emit_map_slots
 
-    batch = DeviceBatch(engine, nbuf=nbuf, buf_len=262144)
+    batch = DeviceBatch(engine, nbuf=nbuf, buf_len=buf_len)
     batch.fill_streams(first_stream=77, bufs_per_stream=8)
-    v = batch.data.view(nbuf, 262144)
+    v = batch.data.view(nbuf, buf_len)
     if holes:
-        v[1, 20000:120000] = 0  # zero chunks repeat inside the buffer (claims > 1)
+        # zero chunks repeat inside the buffer (claims > 1): 20000 .. 120000 of a 256 KiB buffer
+        v[1, 20000 * buf_len // 262144:120000 * buf_len // 262144] = 0
     for b in range(nbuf // 2, nbuf):
         v[b].copy_(v[b - nbuf // 2])
     batch.run(buffer_id_base=0)
@@ -77,13 +78,17 @@ def _run(engine, nbuf, hash_len, slot_len=None, holes=True):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("algo", ["sha256", "md5"])
-def test_gpu_map_images_vs_restatement(algo):
+@pytest.mark.parametrize("algo,nbuf,buf_len", [
+    ("sha256", 32, 262144), ("md5", 32, 262144),
+    # the one-block prefix of the buffers' counts with more than one buffer per thread and a count
+    # that is no multiple of the block: one or two chunks per buffer
+    ("sha256", 1025, 8192),
+], ids=["sha256", "md5", "sha256-1025x8192"])
+def test_gpu_map_images_vs_restatement(algo, nbuf, buf_len):
     from sdfs_amd import HipVariableMD5HashEngine, HipVariableSha256HashEngine
     e = HipVariableMD5HashEngine() if algo == "md5" else HipVariableSha256HashEngine()
     hl = 16 if algo == "md5" else 32
-    nbuf = 32
-    m, doop, ovf, counts, st, ln, dg, dup, loc = _run(e, nbuf, hl)
+    m, doop, ovf, counts, st, ln, dg, dup, loc = _run(e, nbuf, hl, buf_len=buf_len)
     assert ovf == 0
     sb = M.slot_bytes(hl, 262144, 4095)
     want = _host_images(counts, st, ln, dg, dup, loc, hl)
@@ -93,7 +98,7 @@ def test_gpu_map_images_vs_restatement(algo):
         assert not img[len(want[b]):].any()  # the rest of the slot is untouched (zero here)
         assert doop[b] == struct.unpack(">I", want[b][-4:])[0]
     # copied buffers are all duplicates: doop = the whole buffer
-    assert (doop[nbuf // 2:] == 262144).all()
+    assert (doop[nbuf // 2:] == buf_len).all()
     e.destroy()
 
 

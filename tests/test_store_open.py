@@ -374,6 +374,18 @@ def test_gpu_scan_against_the_model(hl, version, pad):
 
 
 @pytest.mark.gpu
+def test_gpu_scan_of_1025_archives():
+    """arc_first is a one-block prefix over the archives' filled slots: 1 025 archives of one record
+    each give its first threads two archives and its last ones none, and are no multiple of the
+    block.  Every output against the model, arc_first and the record list among them."""
+    rng = np.random.default_rng(1025)
+    arcs = [_filled(3, 1, 16, 0, rng) for _ in range(1025)]
+    sc, want, _ = _scan_and_check([bytes(a.data) for a in arcs], [a.map.image() for a in arcs], 16, 0)
+    assert want["arc_first"] == list(range(1026)) and not any(want["status"])
+    assert [r["key"] for r in want["records"]] == [a.order[0] for a in arcs]
+
+
+@pytest.mark.gpu
 def test_gpu_scan_sorts_a_large_map_in_global_memory():
     """16 500 zero-length records of 40 bytes each in one archive: more than the 16 384 (pos, slot)
     pairs the scan sorts in LDS.  (A record of 0 bytes has no nz word: every one is flagged NZ.)"""
