@@ -128,6 +128,84 @@ int sdfs_cdc_index_compact(sdfs_cdc_index* ix, void* stream);
  * output may be NULL.  (AbstractHashesMap.getSize / getMaxSize) */
 int sdfs_cdc_index_stats(sdfs_cdc_index* ix, uint64_t* live, uint64_t* tombstones, uint64_t* capacity);
 
+/* ---- map-file walks: claims straight from slot images, the audit, the way in and out ----
+ *
+ * The reference's file delete (LongByteArrayMap.vanish, LongByteArrayMap.java:817-882), snapshot
+ * (copy(dest, true) -> index() -> nextValue(true), :884-890, :897-940, :310-356), trim (:595-648)
+ * and truncate (:656-688) are walks over a whole map file that call DedupFileStore.removeRef /
+ * addRef(p.hash, hashloc, 1) for every HashLocPair of every slot.  The calls below do that walk
+ * on the device, straight from the slot images.
+ *
+ * An image is read by exactly the rule of sdfs_cdc_map_parse (sdfs_read.h): zlen <= 0 = no pairs;
+ * 13 + zlen * BAL > slot_bytes, or any pair with a negative len / pos / offset / nlen = the slot is
+ * SDFS_CDC_READ_CORRUPT and none of its pairs is applied; an all-zero slot has no pairs and status
+ * 0.  The pairs that count are the TreeMap's: in an image whose pos values are not strictly
+ * ascending, a pair that shares its pos with a later pair of the image does not count (each pair
+ * is then compared with every later one; no writer produces such an image).  hash_len: 32 or 16.
+ * d_sel (may be NULL = every slot): slot s takes part when d_sel[s] != 0; a slot that does not
+ * gets status 0, 0 missed pairs, and keeps every byte.
+ *
+ * Two things the reference does are deliberately NOT mirrored:
+ *   - addRef / removeRef skip hashloc 0 and 1 and the blank hash (DedupFileStore.java:131-136).
+ *     put_records counts those pairs, and 0 / 1 are real positions when pos_base = 0, so here every
+ *     pair counts.
+ *   - nextValue(true) rewrites a pair's hashloc when addRef answers another value.  The claim here
+ *     matches only an equal pos, so there is nothing to rewrite: the images are never edited.
+ */
+
+/* claimKey(hash, hashloc, delta) for every counting pair of the selected slots of the image
+ * d_map (nslots x slot_bytes on the device): a digest that is held with pos == hashloc has delta
+ * (non-zero) added to its count; any other pair changes nothing and is "missed" (the reference's
+ * claimKey == -1, counted by vanish as "unable to remove orphaned reference").
+ * d_slot_status[s] (required) = 0 or SDFS_CDC_READ_CORRUPT; d_slot_missed[s] (may be NULL) = the
+ * slot's missed pairs; d_counts (required, device u64[4]) = {pairs applied, pairs missed, corrupt
+ * slots, selected slots with at least one pair}.  With free_slots != 0 every selected slot whose
+ * status is 0 is then overwritten with slot_bytes zeros (LongByteArrayMap.FREE; what trim does):
+ * corrupt and unselected slots keep every byte (the reference's trim logs the exception and
+ * stops at a corrupt slot; the batch flags the slot and goes on).  Validation is a kernel of its
+ * own before any count moves, so the result does not depend on the schedule.  A slot with
+ * thousands of pairs (the backup profile's 20 484) is spread over several waves. */
+int sdfs_cdc_index_claim_slots(sdfs_cdc_index* ix, uint8_t* d_map, uint64_t nslots, uint32_t slot_bytes,
+                               uint32_t hash_len, const uint8_t* d_sel, int64_t delta, int free_slots,
+                               uint32_t* d_slot_status, uint32_t* d_slot_missed, uint64_t* d_counts,
+                               void* stream);
+
+/* The audit: do the counts still match the files?  The same walk, but every counting pair whose
+ * digest is held at pos == hashloc adds 1 to a shadow count of that fingerprint (zeroed by this
+ * call; any other pair is missed); then every held entry's count (have) is compared with its
+ * shadow (want).  d_counts (required, device u64[8]) = {pairs counted, pairs missed, corrupt
+ * slots, entries with have < want, entries with have > want, entries with want == 0, entries
+ * equal, mismatches listed}.  The first `cap` entries with have != want in table-slot order go to
+ * d_mis_digests (cap x 32), d_mis_pos, d_mis_have, d_mis_want (int64; all four may be NULL when
+ * cap = 0).  With repair != 0 every held entry's count is then set to its want: entries nobody
+ * names go to 0 and the next sdfs_cdc_index_sweep collects them.  The counts and the list describe
+ * the state BEFORE the repair.
+ * The caller's duty: the image must hold every persisted slot of the volume — every file's map,
+ * snapshots included — or entries named only by the slots left out read as over-counted (and a
+ * repair would hand them to the sweep).
+ * The shadow lives in the 8 spare bytes of the fingerprint's own 64-byte table slot: no
+ * allocation (so no SDFS_CDC_ENOMEM), and the add lands in the cache line the probe fetched. */
+int sdfs_cdc_index_recount(sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t nslots, uint32_t slot_bytes,
+                           uint32_t hash_len, const uint8_t* d_sel, int repair, uint32_t* d_slot_status,
+                           uint32_t* d_slot_missed, uint8_t* d_mis_digests, uint64_t* d_mis_pos,
+                           int64_t* d_mis_have, int64_t* d_mis_want, uint64_t cap, uint64_t* d_counts,
+                           void* stream);
+
+/* The way in with explicit positions (a restart from the system of record's iteration, or from
+ * an export).  Item i = {d_digests[i*32 .. +32), d_pos[i], d_ref[i]}.  A digest that is not held
+ * is inserted; its pos is the smallest d_pos among the items of this call that name it.  Then for
+ * every item: the entry's pos == d_pos[i] -> its count += d_ref[i], d_status[i] = 0; otherwise
+ * nothing is added and d_status[i] = 1 (conflict).  The outcome is a function of the arguments
+ * alone.  Fill, the rebuild before SDFS_CDC_ECAP and SDFS_CDC_ENOMEM are as for put_records. */
+int sdfs_cdc_index_load(sdfs_cdc_index* ix, const uint8_t* d_digests, const uint64_t* d_pos,
+                        const int64_t* d_ref, uint64_t n, uint8_t* d_status, void* stream);
+
+/* The way out: every held entry, those with count <= 0 included, in table-slot order; the first
+ * `cap` are written to d_digests (cap x 32), d_pos, d_ref (may be NULL when cap = 0).
+ * d_n (required, device u64[2]) = {written, held}. */
+int sdfs_cdc_index_export(sdfs_cdc_index* ix, uint8_t* d_digests, uint64_t* d_pos, int64_t* d_ref,
+                          uint64_t cap, uint64_t* d_n, void* stream);
+
 /* Test hook: the batch epoch counter (31 bits; the next put_records uses epoch + 1, wrapping to 1).
  * Stamps only mark a batch's own insertions while it runs, so any value is safe. */
 int sdfs_cdc_index_set_epoch(sdfs_cdc_index* ix, uint32_t epoch);

@@ -263,6 +263,12 @@ SIGNATURES = {
     "sdfs_cdc_index_sweep": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "sdfs_cdc_index_compact": (ctypes.c_int, [_vp, _vp]),
     "sdfs_cdc_index_stats": (ctypes.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "sdfs_cdc_index_claim_slots": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                                  ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_index_recount": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                              ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_index_load": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_index_export": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     # include/sdfs_lz4.h
     "sdfs_cdc_lz4_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
     "sdfs_cdc_lz4_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P(_vp)]),

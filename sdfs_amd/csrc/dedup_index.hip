@@ -34,14 +34,23 @@
 // Tombstones count against the fill; a rebuild copies the committed slots into a transient second
 // table (one CAS on `state` per entry, no key compares: all keys are distinct) and back.  Every
 // phase that reads what another workgroup wrote is its own kernel on the same stream.
+//
+// Whole-map-file walks (LongByteArrayMap.vanish / index / trim / truncate, LongByteArrayMap.java:
+// 817-882, 897-940, 595-648, 656-688) claim straight from slot images: validate (one wave per
+// slot), then apply (a wave per kWalkPart pairs).  recount is the same walk pointed at a shadow
+// count in each slot's spare bytes, followed by a count / scan / emit over the table; load and
+// export are the way in and out with the caller's positions.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <mutex>
 
 #include "../../include/sdfs_index.h"
+#include "call_support.h"
 #include "cdc_internal.h"
+#include "store_format.h"
 #include "stream_order.h"
 
 namespace sdfs {
@@ -54,9 +63,11 @@ struct alignas(64) IndexSlot {
     uint32_t state;   // 0 = empty, kCommitted = holds a fingerprint, kTombstone = swept (the key is
                       // stale; probes step over it), (epoch << 1) | 1 (epoch >= 1) = being inserted
                       // by the batch of that epoch
-    uint32_t pad[3];
+    uint32_t pad;
+    uint64_t shadow;  // recount's count of the pairs that name this fingerprint (zeroed by each recount)
 };
 static_assert(sizeof(IndexSlot) == 64, "one cache line per slot");
+static_assert(offsetof(IndexSlot, shadow) == 56, "the shadow count rides in the slot's spare bytes");
 
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr uint32_t kCommitted = 1u;  // never a batch stamp: those are >= 3
@@ -393,6 +404,389 @@ __global__ __launch_bounds__(kIxThreads) void ix_rebuild_kernel(const IndexSlot*
     }
 }
 
+// ---------------------------------------------------------------------------- map-file walks
+//
+// claim_slots and recount read HashLocPairs straight from slot images (store_format.h), by the
+// rule of map_parse_kernel (read_path.hip).  Validation is a kernel of its own (one wave per
+// slot): it settles every slot's status and pair count before any count moves.  The apply pass
+// gives a wave kWalkPart pairs of one slot, so a slot of thousands of pairs spreads over many
+// waves; a lane realigns its pair's hash and hashloc from aligned dword loads (pairs start at
+// odd byte offsets) and probes; a run of neighbouring lanes that found the same entry adds once,
+// with one 64-bit device-scope atomic.  Integer adds commute: the outcome does not depend on the
+// schedule.
+
+constexpr int kWalkThreads = 256;                 // four waves, each on its own slot (part)
+constexpr uint32_t kWalkPart = 256;               // pairs of one slot a wave of the apply pass takes
+constexpr uint32_t kWalkUnsorted = 0x80000000u;   // meta: the image's pos values are not strictly ascending
+
+struct WalkArgs {
+    const uint8_t* map;
+    uint64_t nslots;
+    uint32_t slot_bytes;
+    uint32_t hash_len;
+    const uint8_t* sel;
+    uint32_t* status;    // [nslots]
+    uint32_t* missed;    // [nslots] or NULL
+    uint32_t* meta;      // [nslots] scratch: pairs to apply | kWalkUnsorted
+    uint64_t* counts;    // [0] applied, [1] missed, [2] corrupt slots
+    uint64_t* nonempty;  // selected slots with at least one pair, or NULL
+    uint32_t parts;      // waves per slot in the apply pass
+};
+
+// N 32-bit words from p, whatever its alignment: aligned loads realigned by a byte shift.  Every
+// word loaded holds at least one of the bytes asked for.
+template <int N>
+__device__ __forceinline__ void load_words(const uint8_t* p, uint32_t (&w)[N]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const uint32_t r = (uint32_t)(a & 3);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(a - r);
+    uint32_t t[N + 1];
+#pragma unroll
+    for (int i = 0; i < N; i++) t[i] = q[i];
+    t[N] = r ? q[N] : 0u;
+#pragma unroll
+    for (int i = 0; i < N; i++) w[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], r);
+}
+
+__global__ __launch_bounds__(kWalkThreads) void ix_walk_validate_kernel(WalkArgs a) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * (kWalkThreads / 64) + (threadIdx.x >> 6);
+    if (s >= a.nslots) return;  // wave-uniform, as is every branch below
+    const uint32_t hl = a.hash_len;
+    uint32_t status = 0, n = 0;
+    bool unsorted = false;
+    if (!a.sel || a.sel[s]) {
+        const uint8_t* img = a.map + s * a.slot_bytes;
+        const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
+        if (zlen > 0) {
+            if (slot_need((uint32_t)zlen, hl) > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;
+            else n = (uint32_t)zlen;
+        }
+        bool neg = false;
+        for (uint32_t i = lane; i < n; i += 64) {
+            const uint8_t* q = pair_fields(img, i, hl);
+            const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
+            neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
+                    (int32_t)get_be32(q + kPairNlenAt)) < 0;
+            if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hl) + kPairPosAt) >= ps;
+        }
+        if (__ballot(neg) != 0) {  // HashLocPair.checkCorrupt
+            status = SDFS_CDC_READ_CORRUPT;
+            n = 0;
+        }
+        unsorted = __ballot(unsorted) != 0;
+    }
+    if (lane == 0) {
+        a.status[s] = status;
+        if (a.missed) a.missed[s] = 0;
+        a.meta[s] = n | (n && unsorted ? kWalkUnsorted : 0u);
+        if (status) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[2]), 1ull);
+        if (n && a.nonempty) atomicAdd(reinterpret_cast<unsigned long long*>(a.nonempty), 1ull);
+    }
+}
+
+// HW: words of a pair's hash (8 = SHA-256, 4 = MD5).  SHADOW: recount (+1 on the entry's shadow
+// count) instead of claim (delta on its count).
+template <int HW, bool SHADOW>
+__global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a, IndexSlot* table, uint64_t cmask,
+                                                                     int64_t delta) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t unit = (uint64_t)blockIdx.x * (kWalkThreads / 64) + (threadIdx.x >> 6);
+    const uint64_t s = unit / a.parts;
+    if (s >= a.nslots) return;  // wave-uniform
+    const uint32_t meta = a.meta[s];
+    const uint32_t n = meta & ~kWalkUnsorted;
+    const uint32_t i0 = (uint32_t)(unit % a.parts) * kWalkPart;
+    if (i0 >= n) return;
+    const uint32_t i1 = min(n, i0 + kWalkPart);
+    constexpr uint32_t hl = HW * 4;
+    const uint8_t* img = a.map + s * a.slot_bytes;
+    uint32_t applied = 0, missed = 0;
+    for (uint32_t ib = i0; ib < i1; ib += 64) {  // the same trip count for every lane of the wave
+        const uint32_t i = ib + lane;
+        bool on = i < i1;
+        if (on && (meta & kWalkUnsorted)) {  // TreeMap.put: a later pair with the same pos replaces this one
+            const uint32_t ps = get_be32(pair_fields(img, i, hl) + kPairPosAt);
+            bool dead = false;
+            for (uint32_t j = i + 1; j < n; j++) dead |= get_be32(pair_fields(img, j, hl) + kPairPosAt) == ps;
+            on = !dead;
+        }
+        bool hit = false;
+        uint32_t at = 0;  // the entry's table slot (slots <= 2^31)
+        if (on) {
+            uint32_t w[HW + 2];  // hash | BE64 hashloc
+            load_words(slot_pair(img, i, hl), w);
+            const uint4 ka = make_uint4(w[0], w[1], w[2], w[3]);
+            const uint4 kb = HW == 8 ? make_uint4(w[HW - 4], w[HW - 3], w[HW - 2], w[HW - 1]) : make_uint4(0, 0, 0, 0);
+            const uint64_t hashloc = (uint64_t)__builtin_bswap32(w[HW]) << 32 | __builtin_bswap32(w[HW + 1]);
+            uint64_t h = mix64((uint64_t)ka.y << 32 | ka.x) & cmask;
+            for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
+                const IndexSlot& e = table[h];
+                const uint32_t st = e.state;
+                if (st == 0) break;
+                if (st == kTombstone) continue;
+                if (eq4(e.key[0], ka) && eq4(e.key[1], kb)) {
+                    hit = e.pos == hashloc;  // claimKey: the right archive
+                    at = (uint32_t)h;
+                    break;
+                }
+            }
+        }
+        // A run of neighbouring pairs that name one entry — a stretch of all-zero chunks — adds
+        // once, from its first lane, not lane by lane on one address.  Pairs are in pos order, so a
+        // repeated chunk sits in neighbouring lanes; equal entries further apart add separately.
+        const uint32_t prev_at = __shfl_up(at, 1);
+        const unsigned long long hits = __ballot(hit);
+        const bool head = hit && (lane == 0 || !((hits >> (lane - 1)) & 1) || prev_at != at);
+        const unsigned long long stops = __ballot(head) | ~hits;  // lanes at which a run ends
+        if (head) {
+            const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
+            const unsigned long long k = above ? (unsigned long long)__ffsll((long long)above) : 64ull - lane;
+            IndexSlot& e = table[at];
+            atomicAdd(reinterpret_cast<unsigned long long*>(SHADOW ? &e.shadow : &e.ref),
+                      SHADOW ? k : (unsigned long long)delta * k);
+        }
+        applied += hit;
+        missed += on && !hit;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        applied += __shfl_xor(applied, o);
+        missed += __shfl_xor(missed, o);
+    }
+    if (lane == 0) {
+        if (applied) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[0]), (unsigned long long)applied);
+        if (missed) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[1]), (unsigned long long)missed);
+            if (a.missed) atomicAdd(&a.missed[s], missed);
+        }
+    }
+}
+
+// trim: every selected slot that parsed becomes LongByteArrayMap.FREE (zeros); one workgroup per slot
+__global__ __launch_bounds__(kWalkThreads) void ix_walk_free_kernel(uint8_t* map, uint32_t slot_bytes,
+                                                                    const uint8_t* sel, const uint32_t* status) {
+    const uint64_t s = blockIdx.x;
+    if ((sel && !sel[s]) || status[s]) return;
+    uint8_t* p = map + s * slot_bytes;
+    const uint32_t head = min(slot_bytes, (uint32_t)((0 - reinterpret_cast<uintptr_t>(p)) & 15));
+    const uint32_t nvec = (slot_bytes - head) / 16;
+    for (uint32_t i = threadIdx.x; i < head; i += kWalkThreads) p[i] = 0;
+    uint4* v = reinterpret_cast<uint4*>(p + head);
+    for (uint32_t i = threadIdx.x; i < nvec; i += kWalkThreads) v[i] = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = head + nvec * 16 + threadIdx.x; i < slot_bytes; i += kWalkThreads) p[i] = 0;
+}
+
+__global__ __launch_bounds__(kIxThreads) void ix_shadow_zero_kernel(IndexSlot* table, uint64_t slots) {
+    const uint64_t i = (uint64_t)blockIdx.x * kIxThreads + threadIdx.x;
+    if (i < slots) table[i].shadow = 0;
+}
+
+// ------------------------------------------------------------- lists in table-slot order
+//
+// recount's mismatch list and export use the sweep's count / scan / emit over the slots, so the
+// caller's cap is exact and the order is the table's.
+
+enum : int { kFlagHeld, kFlagMismatch };
+
+// flags per block of kRankBlock slots; for kFlagMismatch also recount's four entry counts
+// (counts[3..6] = have < want, have > want, want == 0, equal)
+template <int KIND>
+__global__ __launch_bounds__(kRankBlock) void ix_flag_count_kernel(const IndexSlot* table, uint64_t slots,
+                                                                   uint32_t* bsum, unsigned long long* flags,
+                                                                   uint64_t* counts) {
+    __shared__ uint32_t lds[64];
+    __shared__ uint32_t cat[4];
+    const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
+    if (KIND == kFlagMismatch && threadIdx.x < 4) cat[threadIdx.x] = 0;
+    const bool held = i < slots && table[i].state == kCommitted;
+    uint32_t f = held;
+    if (KIND == kFlagMismatch) {
+        __syncthreads();
+        const int64_t have = held ? (int64_t)table[i].ref : 0, want = held ? (int64_t)table[i].shadow : 0;
+        f = held && have != want;
+        const bool c[4] = {held && have < want, held && have > want, held && want == 0, held && have == want};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t m = (uint32_t)__popcll(__ballot(c[k]));
+            if ((threadIdx.x & 63) == 0 && m) atomicAdd(&cat[k], m);
+        }
+    }
+    const unsigned long long m = __ballot(f);
+    if ((threadIdx.x & 63) == 0) flags[i >> 6] = m;
+    uint32_t total;
+    (void)block_exclusive_scan(f, lds, total);  // its barriers also order the adds to cat[]
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+    if (KIND == kFlagMismatch && threadIdx.x < 4 && cat[threadIdx.x])
+        atomicAdd(reinterpret_cast<unsigned long long*>(&counts[3 + threadIdx.x]), (unsigned long long)cat[threadIdx.x]);
+}
+
+// exclusive scan of the block counts (one block); *listed = min(total, cap), *total_out = total
+__global__ __launch_bounds__(kRankBlock) void ix_flag_scan_kernel(uint32_t* bsum, uint32_t nblocks, uint64_t cap,
+                                                                  uint64_t* listed, uint64_t* total_out) {
+    __shared__ uint32_t lds[64];
+    uint64_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblocks; b0 += kRankBlock) {
+        const uint32_t i = b0 + threadIdx.x;
+        const uint32_t v = i < nblocks ? bsum[i] : 0u;
+        uint32_t total;
+        const uint32_t ex = block_exclusive_scan(v, lds, total);
+        if (i < nblocks) bsum[i] = (uint32_t)carry + ex;  // flagged entries <= slots <= 2^31
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        *listed = carry < cap ? carry : cap;
+        if (total_out) *total_out = carry;
+    }
+}
+
+// recount: the first `cap` mismatching entries in slot order; then (repair) count = shadow for
+// every held entry
+__global__ __launch_bounds__(kRankBlock) void ix_recount_emit_kernel(IndexSlot* table, uint64_t slots,
+                                                                     const uint32_t* bbase,
+                                                                     const unsigned long long* flags, uint64_t cap,
+                                                                     uint8_t* digests, uint64_t* pos, int64_t* have,
+                                                                     int64_t* want, int repair) {
+    __shared__ uint32_t lds[64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
+    const uint32_t f = (uint32_t)(flags[i >> 6] >> (threadIdx.x & 63)) & 1u;  // set only for i < slots
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    if (!f) return;  // an entry that is equal needs no repair either
+    IndexSlot& s = table[i];
+    const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
+    if (rank < cap) {
+        uint4* d = reinterpret_cast<uint4*>(digests + rank * 32);
+        d[0] = s.key[0];
+        d[1] = s.key[1];
+        pos[rank] = s.pos;
+        have[rank] = (int64_t)s.ref;
+        want[rank] = (int64_t)s.shadow;
+    }
+    if (repair) s.ref = s.shadow;
+}
+
+__global__ __launch_bounds__(kRankBlock) void ix_export_emit_kernel(const IndexSlot* table, uint64_t slots,
+                                                                    const uint32_t* bbase,
+                                                                    const unsigned long long* flags, uint64_t cap,
+                                                                    uint8_t* digests, uint64_t* pos, int64_t* ref) {
+    __shared__ uint32_t lds[64];
+    const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
+    const uint32_t f = (uint32_t)(flags[i >> 6] >> (threadIdx.x & 63)) & 1u;
+    uint32_t total;
+    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    if (!f) return;
+    const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
+    if (rank >= cap) return;
+    const IndexSlot& s = table[i];
+    uint4* d = reinterpret_cast<uint4*>(digests + rank * 32);
+    d[0] = s.key[0];
+    d[1] = s.key[1];
+    pos[rank] = s.pos;
+    ref[rank] = (int64_t)s.ref;
+}
+
+// ---------------------------------------------------------------------------------------- load
+//
+// Items {digest, pos, count} with the caller's positions.  As in put_records, equal digests of the
+// call first meet in a batch-local table of ITEM INDICES (which also takes the smallest pos of the
+// group), then one representative per group probes the global table and, where the digest is
+// absent, claims a slot under the batch's stamp with that smallest pos; the last kernel adds every
+// item's count where its pos is the entry's, and commits the stamped slots.
+
+__device__ __forceinline__ void load_digest32(const uint8_t* digests, uint32_t i, uint4& a, uint4& b) {
+    const uint4* p = reinterpret_cast<const uint4*>(digests + (uint64_t)i * 32);
+    a = p[0];
+    b = p[1];
+}
+
+__global__ __launch_bounds__(kIxThreads) void ix_load_group_kernel(const uint8_t* digests, const uint64_t* pos,
+                                                                   uint32_t n, uint32_t* ltab,
+                                                                   unsigned long long* lminpos, uint32_t lmask,
+                                                                   uint32_t* lslot) {
+    const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
+    if (r >= n) return;
+    uint4 a, b;
+    load_digest32(digests, r, a, b);
+    uint32_t h = (uint32_t)mix64(((uint64_t)a.w << 32 | a.z) ^ 0x5DF50001ull) & lmask;
+    for (;;) {  // lmask + 1 >= 2n: an empty slot always exists
+        uint32_t v = ltab[h];
+        if (v == kEmpty) {
+            const uint32_t old = atomicCAS(&ltab[h], kEmpty, r);
+            if (old == kEmpty) break;
+            v = old;
+        }
+        uint4 c, d;
+        load_digest32(digests, v, c, d);
+        if (eq4(a, c) && eq4(b, d)) {
+            atomicMin(&ltab[h], r);
+            break;
+        }
+        h = (h + 1) & lmask;
+    }
+    atomicMin(&lminpos[h], (unsigned long long)pos[r]);
+    lslot[r] = h;
+}
+
+__global__ __launch_bounds__(kIxThreads) void ix_load_probe_kernel(const uint8_t* digests, uint32_t n,
+                                                                   const uint32_t* ltab,
+                                                                   const unsigned long long* lminpos,
+                                                                   const uint32_t* lslot, IndexSlot* table,
+                                                                   uint64_t cmask, uint32_t stamp, uint32_t* gidx,
+                                                                   uint64_t* used, uint32_t* overflow) {
+    const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t ls = lslot[r];
+    if (ltab[ls] != r) return;  // not the representative of its digest
+    uint4 a, b;
+    load_digest32(digests, r, a, b);
+    uint64_t h = mix64((uint64_t)a.y << 32 | a.x) & cmask;
+    for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
+        IndexSlot& s = table[h];
+        uint32_t st = s.state;
+        if (st == 0) {
+            const uint32_t old = atomicCAS(&s.state, 0u, stamp);
+            if (old == 0) {
+                s.key[0] = a;
+                s.key[1] = b;
+                s.ref = 0;
+                s.pos = lminpos[ls];
+                gidx[ls] = (uint32_t)h;
+                atomicAdd(reinterpret_cast<unsigned long long*>(used), 1ull);
+                return;
+            }
+            st = old;
+        }
+        if (st == stamp) continue;       // inserted by this call: a different digest
+        if (st == kTombstone) continue;  // swept: the chain goes on, the key is stale
+        if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
+            gidx[ls] = (uint32_t)h;
+            return;
+        }
+    }
+    atomicOr(overflow, 1u);
+    gidx[ls] = 0xFFFFFFFFu;
+}
+
+__global__ __launch_bounds__(kIxThreads) void ix_load_apply_kernel(const uint64_t* pos, const int64_t* ref, uint32_t n,
+                                                                   const uint32_t* ltab, const uint32_t* lslot,
+                                                                   const uint32_t* gidx, IndexSlot* table,
+                                                                   uint32_t stamp, uint8_t* status) {
+    const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t ls = lslot[r];
+    const uint32_t g = gidx[ls];
+    if (g == 0xFFFFFFFFu) {
+        status[r] = 1;
+        return;
+    }
+    IndexSlot& s = table[g];
+    const bool ok = s.pos == pos[r];
+    if (ok) atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)ref[r]);
+    status[r] = ok ? 0 : 1;
+    if (ltab[ls] == r && s.state == stamp) s.state = kCommitted;  // the stamp must not survive the call
+}
+
 template <typename T>
 struct IxBuf {
     T* p = nullptr;
@@ -439,6 +833,7 @@ struct sdfs_cdc_index {
     IxBuf<uint32_t> ltab, lcount, lslot, gidx, isnew, bsum, overflow;
     IxBuf<uint32_t> sweep_bsum;  // dead entries per kRankBlock slots (allocated with the table)
     IxBuf<unsigned long long> sweep_dead;  // the slots' dead flags, one word per 64 slots (likewise)
+    IxBuf<unsigned long long> lminpos;     // load: the smallest pos of each group of equal digests
     hipStream_t own = nullptr;   // the index's own non-blocking stream: set-up and readbacks
     hipStream_t last = nullptr;  // the stream of the latest batch (own until one comes)
     StreamOrder order;  // batches apply in call order whatever streams they come on
@@ -498,7 +893,183 @@ static int rebuild_on(sdfs_cdc_index* ix, hipStream_t s) {
     return SDFS_CDC_OK;
 }
 
+// The fill rule of a batch that may insert up to n fingerprints (put_records, load), then the
+// batch's place in the call order on s: ECAP when the batch does not fit the fingerprints held;
+// when it fits those but not those plus the tombstones, a rebuild is enqueued first.  The caller
+// holds ix->mu.
+static int make_room(sdfs_cdc_index* ix, hipStream_t s, uint64_t n) {
+    bool rebuild = false;
+    if (ix->used_ub + ix->tomb_ub + n > ix->max_fill) {  // refresh the bounds from the device counts
+        IX_TRY(hipStreamSynchronize(s));
+        uint64_t used = 0, tombs = 0;
+        uint32_t ovf = 0;
+        const int rc = read_counts(ix, &used, &tombs, &ovf);
+        if (rc != SDFS_CDC_OK) return rc;
+        if (ovf) return fail_status(SDFS_CDC_ECAP, "index overflowed");
+        if (used + n > ix->max_fill)
+            return fail_status(SDFS_CDC_ECAP, "index full: %llu of %llu fingerprints held, batch of %llu",
+                               (unsigned long long)used, (unsigned long long)ix->max_fill,
+                               (unsigned long long)n);
+        // the batch fits the fingerprints held but not those plus the tombstones: drop them first
+        rebuild = used + tombs + n > ix->max_fill;
+    }
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    if (rebuild) return rebuild_on(ix, s);
+    return SDFS_CDC_OK;
+}
+
+// The argument checks the two walks share (before the device is touched).
+static int check_walk(const sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t nslots, uint32_t slot_bytes,
+                      uint32_t hash_len, const uint32_t* d_slot_status, const uint64_t* d_counts) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    if (const int rc = check_hash_len(hash_len, HashOf::kPair)) return rc;
+    if (slot_bytes < kSlotFixedBytes) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
+    if (!d_slot_status || !d_counts) return fail_status(SDFS_CDC_EINVAL, "null slot_status or counts");
+    if (nslots && !d_map) return fail_status(SDFS_CDC_EINVAL, "null map");
+    const uint64_t parts = (pair_cap(slot_bytes, hash_len) + kWalkPart - 1) / kWalkPart;
+    if (nslots >= (1ull << 31) || nslots * std::max<uint64_t>(parts, 1) >= (1ull << 32))
+        return fail_status(SDFS_CDC_EINVAL, "%llu slots of %u bytes: split the image", (unsigned long long)nslots,
+                           slot_bytes);
+    return SDFS_CDC_OK;
+}
+
+// Validate, then apply, on s.  a.meta is filled in here; the caller has zeroed a.counts.
+template <bool SHADOW>
+static int launch_walk(sdfs_cdc_index* ix, hipStream_t s, Scratch& sc, WalkArgs a, int64_t delta) {
+    a.parts = std::max<uint32_t>(1, (pair_cap(a.slot_bytes, a.hash_len) + kWalkPart - 1) / kWalkPart);
+    SDFS_TRY(sc.get(&a.meta, (size_t)a.nslots));
+    constexpr uint32_t wpb = kWalkThreads / 64;
+    hipLaunchKernelGGL(ix_walk_validate_kernel, dim3((uint32_t)((a.nslots + wpb - 1) / wpb)), dim3(kWalkThreads), 0, s,
+                       a);
+    const dim3 grid((uint32_t)((a.nslots * a.parts + wpb - 1) / wpb));
+    if (a.hash_len == 32)
+        hipLaunchKernelGGL((ix_walk_apply_kernel<8, SHADOW>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
+                           ix->slots - 1, delta);
+    else
+        hipLaunchKernelGGL((ix_walk_apply_kernel<4, SHADOW>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
+                           ix->slots - 1, delta);
+    IX_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
 extern "C" {
+
+int sdfs_cdc_index_claim_slots(sdfs_cdc_index* ix, uint8_t* d_map, uint64_t nslots, uint32_t slot_bytes,
+                               uint32_t hash_len, const uint8_t* d_sel, int64_t delta, int free_slots,
+                               uint32_t* d_slot_status, uint32_t* d_slot_missed, uint64_t* d_counts, void* stream) {
+    if (const int rc = check_walk(ix, d_map, nslots, slot_bytes, hash_len, d_slot_status, d_counts)) return rc;
+    if (delta == 0) return fail_status(SDFS_CDC_EINVAL, "delta 0 claims nothing");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    IX_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(uint64_t), s));
+    if (nslots) {
+        Scratch sc(s);
+        WalkArgs a{d_map, nslots, slot_bytes, hash_len, d_sel, d_slot_status, d_slot_missed, nullptr, d_counts,
+                   d_counts + 3, 1};
+        if (const int rc = launch_walk<false>(ix, s, sc, a, delta)) return rc;
+        if (free_slots) {
+            hipLaunchKernelGGL(ix_walk_free_kernel, dim3((uint32_t)nslots), dim3(kWalkThreads), 0, s, d_map, slot_bytes,
+                               d_sel, d_slot_status);
+            IX_TRY(hipGetLastError());
+        }
+    }
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_recount(sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t nslots, uint32_t slot_bytes,
+                           uint32_t hash_len, const uint8_t* d_sel, int repair, uint32_t* d_slot_status,
+                           uint32_t* d_slot_missed, uint8_t* d_mis_digests, uint64_t* d_mis_pos, int64_t* d_mis_have,
+                           int64_t* d_mis_want, uint64_t cap, uint64_t* d_counts, void* stream) {
+    if (const int rc = check_walk(ix, d_map, nslots, slot_bytes, hash_len, d_slot_status, d_counts)) return rc;
+    if (cap && (!d_mis_digests || !d_mis_pos || !d_mis_have || !d_mis_want))
+        return fail_status(SDFS_CDC_EINVAL, "null mismatch list");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    IX_TRY(hipMemsetAsync(d_counts, 0, 8 * sizeof(uint64_t), s));
+    hipLaunchKernelGGL(ix_shadow_zero_kernel, dim3((uint32_t)((ix->slots + kIxThreads - 1) / kIxThreads)),
+                       dim3(kIxThreads), 0, s, ix->table.p, ix->slots);
+    if (nslots) {
+        Scratch sc(s);
+        WalkArgs a{d_map, nslots, slot_bytes, hash_len, d_sel, d_slot_status, d_slot_missed, nullptr, d_counts,
+                   nullptr, 1};
+        if (const int rc = launch_walk<true>(ix, s, sc, a, 0)) return rc;
+    }
+    const uint32_t nb = (uint32_t)((ix->slots + kRankBlock - 1) / kRankBlock);
+    hipLaunchKernelGGL(ix_flag_count_kernel<kFlagMismatch>, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                       ix->sweep_bsum.p, ix->sweep_dead.p, d_counts);
+    hipLaunchKernelGGL(ix_flag_scan_kernel, dim3(1), dim3(kRankBlock), 0, s, ix->sweep_bsum.p, nb, cap, d_counts + 7,
+                       (uint64_t*)nullptr);
+    if (cap || repair)
+        hipLaunchKernelGGL(ix_recount_emit_kernel, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                           ix->sweep_bsum.p, ix->sweep_dead.p, cap, d_mis_digests, d_mis_pos, d_mis_have, d_mis_want,
+                           repair);
+    IX_TRY(hipGetLastError());
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_load(sdfs_cdc_index* ix, const uint8_t* d_digests, const uint64_t* d_pos, const int64_t* d_ref,
+                        uint64_t n, uint8_t* d_status, void* stream) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    if (n && (!d_digests || !d_pos || !d_ref || !d_status)) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n >= (1ull << 31)) return fail_status(SDFS_CDC_EINVAL, "batch too large");
+    if (n == 0) return SDFS_CDC_OK;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = make_room(ix, s, n)) return rc;
+    const uint64_t lsize = std::max<uint64_t>(64, next_pow2(2 * n));
+    if (ix->ltab.ensure(lsize) != hipSuccess || ix->lminpos.ensure(lsize) != hipSuccess ||
+        ix->gidx.ensure(lsize) != hipSuccess || ix->lslot.ensure(n) != hipSuccess)
+        return fail_status(SDFS_CDC_ENOMEM, "index scratch allocation failed");
+    ix->epoch = (ix->epoch + 1) & 0x7FFFFFFFu;
+    if (ix->epoch == 0) ix->epoch = 1;
+    const uint32_t stamp = (ix->epoch << 1) | 1u;
+    IX_TRY(hipMemsetAsync(ix->ltab.p, 0xFF, lsize * sizeof(uint32_t), s));
+    IX_TRY(hipMemsetAsync(ix->lminpos.p, 0xFF, lsize * sizeof(unsigned long long), s));
+    const uint32_t g = (uint32_t)((n + kIxThreads - 1) / kIxThreads);
+    hipLaunchKernelGGL(ix_load_group_kernel, dim3(g), dim3(kIxThreads), 0, s, d_digests, d_pos, (uint32_t)n, ix->ltab.p,
+                       ix->lminpos.p, (uint32_t)(lsize - 1), ix->lslot.p);
+    hipLaunchKernelGGL(ix_load_probe_kernel, dim3(g), dim3(kIxThreads), 0, s, d_digests, (uint32_t)n, ix->ltab.p,
+                       ix->lminpos.p, ix->lslot.p, ix->table.p, ix->slots - 1, stamp, ix->gidx.p, ix->used.p,
+                       ix->overflow.p);
+    hipLaunchKernelGGL(ix_load_apply_kernel, dim3(g), dim3(kIxThreads), 0, s, d_pos, d_ref, (uint32_t)n, ix->ltab.p,
+                       ix->lslot.p, ix->gidx.p, ix->table.p, stamp, d_status);
+    IX_TRY(hipGetLastError());
+    IX_TRY(ix->order.release(s));
+    ix->used_ub += n;
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_export(sdfs_cdc_index* ix, uint8_t* d_digests, uint64_t* d_pos, int64_t* d_ref, uint64_t cap,
+                          uint64_t* d_n, void* stream) {
+    if (!ix) return fail_status(SDFS_CDC_EINVAL, "null index");
+    if (!d_n) return fail_status(SDFS_CDC_EINVAL, "null counts");
+    if (cap && (!d_digests || !d_pos || !d_ref)) return fail_status(SDFS_CDC_EINVAL, "null export list");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    const uint32_t nb = (uint32_t)((ix->slots + kRankBlock - 1) / kRankBlock);
+    hipLaunchKernelGGL(ix_flag_count_kernel<kFlagHeld>, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                       ix->sweep_bsum.p, ix->sweep_dead.p, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(ix_flag_scan_kernel, dim3(1), dim3(kRankBlock), 0, s, ix->sweep_bsum.p, nb, cap, d_n, d_n + 1);
+    if (cap)
+        hipLaunchKernelGGL(ix_export_emit_kernel, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
+                           ix->sweep_bsum.p, ix->sweep_dead.p, cap, d_digests, d_pos, d_ref);
+    IX_TRY(hipGetLastError());
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
 
 int sdfs_cdc_index_create(int device, uint64_t capacity, sdfs_cdc_index** out) {
     if (!out) return fail_status(SDFS_CDC_EINVAL, "null output");
@@ -552,6 +1123,7 @@ int sdfs_cdc_index_destroy(sdfs_cdc_index* ix) {
                     &ix->sweep_bsum})
         b->release();
     ix->sweep_dead.release();
+    ix->lminpos.release();
     ix->order.destroy();
     if (ix->own) (void)hipStreamDestroy(ix->own);
     delete ix;
@@ -568,27 +1140,7 @@ int sdfs_cdc_index_put_records(sdfs_cdc_index* ix, const uint8_t* d_records, uin
     std::lock_guard<std::mutex> lk(ix->mu);
     IX_TRY(hipSetDevice(ix->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    bool rebuild = false;
-    if (ix->used_ub + ix->tomb_ub + n_max > ix->max_fill) {  // refresh the bounds from the device counts
-        IX_TRY(hipStreamSynchronize(s));
-        uint64_t used = 0, tombs = 0;
-        uint32_t ovf = 0;
-        const int rc = read_counts(ix, &used, &tombs, &ovf);
-        if (rc != SDFS_CDC_OK) return rc;
-        if (ovf) return fail_status(SDFS_CDC_ECAP, "index overflowed");
-        if (used + n_max > ix->max_fill)
-            return fail_status(SDFS_CDC_ECAP, "index full: %llu of %llu fingerprints held, batch of %llu",
-                               (unsigned long long)used, (unsigned long long)ix->max_fill,
-                               (unsigned long long)n_max);
-        // the batch fits the fingerprints held but not those plus the tombstones: drop them first
-        rebuild = used + tombs + n_max > ix->max_fill;
-    }
-    IX_TRY(ix->order.acquire(s));
-    ix->last = s;
-    if (rebuild) {
-        const int rc = rebuild_on(ix, s);
-        if (rc != SDFS_CDC_OK) return rc;
-    }
+    if (const int rc = make_room(ix, s, n_max)) return rc;
     if (n_max == 0) {
         IX_TRY(hipMemsetAsync(d_new_count, 0, sizeof(uint64_t), s));
         IX_TRY(ix->order.release(s));

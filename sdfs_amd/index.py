@@ -38,6 +38,49 @@ class IndexStats:
     capacity: int
 
 
+@dataclass
+class SlotClaims:
+    """What ``claim_slots`` did (device tensors; reading a property waits for the device)."""
+
+    counts: object       # int64 [4]: pairs applied, pairs missed, corrupt slots, selected slots with a pair
+    slot_status: object  # int32 [nslots]: 0 or READ_CORRUPT
+    slot_missed: object  # int32 [nslots]: pairs whose digest is not held at their hashloc
+
+    applied = property(lambda self: int(self.counts[0].item()))
+    missed = property(lambda self: int(self.counts[1].item()))
+    corrupt = property(lambda self: int(self.counts[2].item()))
+    nonempty = property(lambda self: int(self.counts[3].item()))
+
+
+@dataclass
+class Recount:
+    """What ``recount`` found (device tensors), describing the state before any repair."""
+
+    counts: object       # int64 [8]: counted, missed, corrupt slots, under, over, unnamed, equal, listed
+    slot_status: object  # int32 [nslots]
+    slot_missed: object  # int32 [nslots]
+    digests: object      # uint8 [cap, 32]: the first counts[7] rows of these four are the mismatches,
+    pos: object          # int64 [cap]       in table-slot order
+    have: object         # int64 [cap]: the index's count
+    want: object         # int64 [cap]: the pairs that name the fingerprint
+
+    counted = property(lambda self: int(self.counts[0].item()))
+    missed = property(lambda self: int(self.counts[1].item()))
+    corrupt = property(lambda self: int(self.counts[2].item()))
+    under = property(lambda self: int(self.counts[3].item()))
+    over = property(lambda self: int(self.counts[4].item()))
+    unnamed = property(lambda self: int(self.counts[5].item()))
+    equal = property(lambda self: int(self.counts[6].item()))
+    listed = property(lambda self: int(self.counts[7].item()))
+
+    def mismatches(self):
+        """[(digest bytes, pos, have, want)] of the listed entries (a host read)."""
+        k = self.listed
+        d = self.digests[:k].cpu().numpy()
+        return [(d[i].tobytes(), p, h, w) for i, (p, h, w) in
+                enumerate(zip(self.pos[:k].tolist(), self.have[:k].tolist(), self.want[:k].tolist()))]
+
+
 class HipHashesMap:
     def __init__(self, capacity: int, device: int = 0):
         self._lib = _lib.load()
@@ -149,6 +192,104 @@ class HipHashesMap:
         _lib.check(self._lib.sdfs_cdc_index_sweep(self._h, digests.data_ptr(), pos.data_ptr(), int(cap),
                                                   counts.data_ptr(), s))
         return digests, pos, counts
+
+    # --- map-file walks, the audit, the way in and out (sdfs_cdc_index_claim_slots ...) --------
+    @staticmethod
+    def _slots_view(m, nslots: int, slot_len: int, sel):
+        """The image's first nslots * slot_len bytes (contiguous uint8) and the mask as uint8."""
+        import torch
+
+        if m.numel() < nslots * slot_len:
+            raise ValueError(f"map holds {m.numel()} bytes, {nslots} slots of {slot_len} need {nslots * slot_len}")
+        if m.dtype != torch.uint8 or not m.is_contiguous():
+            raise ValueError("the slot image is a contiguous uint8 tensor")
+        if sel is not None:
+            sel = sel.to(device=m.device, dtype=torch.uint8).contiguous()
+            if sel.shape[0] != nslots:
+                raise ValueError("one selection flag per slot")
+        return sel
+
+    def claim_slots(self, m, nslots: int, slot_len: int, delta: int, sel=None, free: bool = False,
+                    hash_len: int = 32, stream=None) -> "SlotClaims":
+        """``claimKey(hash, hashloc, delta)`` for every pair of the selected slots of the image
+        ``m`` (device uint8, nslots slots of slot_len bytes), read straight from the image by
+        ``parse_map_slots``' rule.  ``sel``: device mask [nslots] (None: every slot).  ``free``:
+        selected slots that parsed are then overwritten with zeros in ``m`` (FREE).  No host wait:
+        the result's tensors are valid once the stream has got there."""
+        import torch
+
+        sel = self._slots_view(m, nslots, slot_len, sel)
+        dev = m.device
+        status = torch.empty(max(nslots, 1), dtype=torch.int32, device=dev)
+        missed = torch.empty(max(nslots, 1), dtype=torch.int32, device=dev)
+        counts = torch.empty(4, dtype=torch.int64, device=dev)
+        _lib.check(self._lib.sdfs_cdc_index_claim_slots(
+            self._h, m.data_ptr() if nslots else None, int(nslots), int(slot_len), int(hash_len), _lib.ptr(sel),
+            int(delta), 1 if free else 0, status.data_ptr(), missed.data_ptr(), counts.data_ptr(),
+            _lib.stream_of(m, stream)))
+        return SlotClaims(counts, status[:nslots], missed[:nslots])
+
+    def recount(self, m, nslots: int, slot_len: int, sel=None, repair: bool = False, cap: int = 1024,
+                hash_len: int = 32, stream=None) -> "Recount":
+        """The audit (``sdfs_cdc_index_recount``): counts every pair of the image ``m`` — which must
+        hold every persisted slot of the volume — into a shadow count per fingerprint and compares
+        it with the index's count.  The first ``cap`` mismatching entries come back in table-slot
+        order; with ``repair`` every count is then set to what the slots say.  No host wait."""
+        import torch
+
+        sel = self._slots_view(m, nslots, slot_len, sel)
+        dev = m.device
+        cap = int(cap)
+        status = torch.empty(max(nslots, 1), dtype=torch.int32, device=dev)
+        missed = torch.empty(max(nslots, 1), dtype=torch.int32, device=dev)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+        dg = torch.empty(max(cap, 1), 32, dtype=torch.uint8, device=dev)
+        pos, have, want = (torch.empty(max(cap, 1), dtype=torch.int64, device=dev) for _ in range(3))
+        _lib.check(self._lib.sdfs_cdc_index_recount(
+            self._h, m.data_ptr() if nslots else None, int(nslots), int(slot_len), int(hash_len), _lib.ptr(sel),
+            1 if repair else 0, status.data_ptr(), missed.data_ptr(), dg.data_ptr(), pos.data_ptr(), have.data_ptr(),
+            want.data_ptr(), cap, counts.data_ptr(), _lib.stream_of(m, stream)))
+        return Recount(counts, status[:nslots], missed[:nslots], dg, pos, have, want)
+
+    def load(self, digests, pos, ref, stream=None):
+        """``sdfs_cdc_index_load``: entries with the caller's positions (digests uint8 [n, 32], pos and
+        ref int64 [n] on the device).  Returns status uint8 [n]: 0 = the item's count was added to
+        the entry at its pos, 1 = conflict (the digest lives at another pos; nothing added)."""
+        import torch
+
+        n = int(digests.shape[0])
+        dev = digests.device
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            digests = digests.contiguous()
+            pos = pos.to(device=dev, dtype=torch.int64).contiguous()
+            ref = ref.to(device=dev, dtype=torch.int64).contiguous()
+            if pos.shape[0] != n or ref.shape[0] != n:
+                raise ValueError("one pos and one count per digest")
+            _lib.check(self._lib.sdfs_cdc_index_load(self._h, digests.data_ptr(), pos.data_ptr(), ref.data_ptr(), n,
+                                                     status.data_ptr(), _lib.stream_of(digests, stream)))
+        return status
+
+    def export(self, cap=None, stream=None):
+        """``sdfs_cdc_index_export``: every held entry, those with count <= 0 included, in
+        table-slot order: (digests uint8 [k, 32], pos int64 [k], ref int64 [k], held) with k =
+        min(cap, held).  Waits for the export to finish (k comes from the device)."""
+        import torch
+
+        if cap is None:
+            cap = self.stats().live
+        cap = int(cap)
+        dev = torch.device(f"cuda:{self.device}")
+        dg = torch.empty(max(cap, 1), 32, dtype=torch.uint8, device=dev)
+        pos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        ref = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        n = torch.empty(2, dtype=torch.int64, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(self._lib.sdfs_cdc_index_export(self._h, dg.data_ptr(), pos.data_ptr(), ref.data_ptr(), cap,
+                                                   n.data_ptr(), s))
+        self.stats()  # synchronises the export's stream
+        k, held = (int(v) for v in n.tolist())
+        return dg[:k], pos[:k], ref[:k], held
 
     def compact(self, stream=None) -> None:
         """Rebuild the table now, dropping the tombstones (needs as much free device memory as
