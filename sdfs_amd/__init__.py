@@ -20,10 +20,12 @@ from .archive import ArchiveSet, HipBlobArchiver, HipBufferWriter  # noqa: F401
 from .read import HipBufferReader, parse_map_slots  # noqa: F401
 from .store import lookup, open_store, scan_store, scrub  # noqa: F401
 from .extent import copy_extents, rewrite_blocks, split_extent  # noqa: F401
-from .mapfile import index_map, snapshot, trim, truncate, vanish  # noqa: F401
+from .mapfile import close_map, index_map, open_map, snapshot, snapshot_compressed, trim, truncate, vanish  # noqa: F401
+from .lz4_stream import HipLz4BlockStream, compressFile, decompressFile, xxh32  # noqa: F401
 
 __all__ = [
-    "index_map", "snapshot", "vanish", "trim", "truncate",
+    "index_map", "snapshot", "vanish", "trim", "truncate", "close_map", "open_map", "snapshot_compressed",
+    "HipLz4BlockStream", "compressFile", "decompressFile", "xxh32",
     "ArchiveSet", "HipBlobArchiver", "HipBufferWriter", "HipBufferReader", "parse_map_slots",
     "open_store", "scan_store", "lookup", "scrub", "copy_extents", "rewrite_blocks", "split_extent",
     "Finger", "HashFunctionPool", "HipVariableMD5HashEngine", "HipVariableSha256HashEngine", "SdfsConfig",

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
                                for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h",
-                                         "sdfs_extent.h")]
+                                         "sdfs_extent.h", "sdfs_lz4_stream.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -174,6 +174,10 @@ STORE_UNREADABLE = STORE_RANGE | STORE_LEN | STORE_NZ
 STORE_GAP, STORE_SLOTS = 1, 2
 STORE_ECAP = 1
 STORE_SORT_LDS = 16384
+
+# SDFS_CDC_LZ4_STREAM_*: a stream's status word
+LZ4S_TRUNCATED, LZ4S_MAGIC, LZ4S_HEADER, LZ4S_DECODE, LZ4S_CHECKSUM, LZ4S_ROOM = 1, 2, 4, 8, 16, 32
+LZ4S_HEADER_BYTES, LZ4S_SEED, LZ4S_BLOCK = 21, 0x9747B28C, 65536
 
 READ_CORRUPT, READ_MISSING, READ_FETCH, READ_BOUNDS = 1, 2, 4, 8  # SDFS_CDC_READ_*
 READ_NONE = 0xFFFFFFFF
@@ -352,6 +356,16 @@ SIGNATURES = {
                                            _P(Inserts), ctypes.c_uint64, _vp, _P(Pairs), _vp, _vp, _vp]),
     "sdfs_cdc_map_emit_pairs": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, _vp, _vp,
                                                ctypes.c_uint8, _vp, ctypes.c_uint32, _vp, _vp, _vp]),
+    # include/sdfs_lz4_stream.h
+    "sdfs_cdc_lz4_stream_level": (ctypes.c_int, [ctypes.c_uint32]),
+    "sdfs_cdc_lz4_stream_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint32]),
+    "sdfs_cdc_lz4_stream_max_blocks": (ctypes.c_uint64, [ctypes.c_uint64]),
+    "sdfs_cdc_xxh32_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint32, _vp, _vp]),
+    "sdfs_cdc_lz4_stream_compress_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                                           _vp, _vp, _vp]),
+    "sdfs_cdc_lz4_stream_scan_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_lz4_stream_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64,
+                                                             _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// store_format.h — the three on-disk formats of the store layer, each defined here and nowhere
+// store_format.h — the four on-disk formats of the store layer, each defined here and nowhere
 // else (host + device).  Not part of the C-ABI.
 //
 //   slot image     SparseDataChunk.getBytes (SparseDataChunk.java:295-318, HashLocPair.asArray
@@ -8,6 +8,8 @@
 //                  509-539); written by archive_pack.hip, read back by store_open.hip
 //   archive record HashBlobArchive.putChunk (HashBlobArchive.java:1399-1411); laid out and packed by
 //                  archive_pack.hip, checked by store_open.hip
+//   LZ4Block stream a map file at rest, CompressionUtils.compressFile (CompressionUtils.java:127-139):
+//                  lz4-java 1.3.0's LZ4BlockOutputStream; written and read by lz4_stream.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,6 +17,7 @@
 #include <cstdint>
 
 #include "../../include/sdfs_archive.h"
+#include "../../include/sdfs_lz4_stream.h"
 
 namespace sdfs {
 namespace {  // internal linkage: nothing here joins the libraries' exported symbols
@@ -160,6 +163,90 @@ __device__ __forceinline__ uint32_t map_probe_next(uint32_t idx, uint32_t step, 
 constexpr uint32_t kRecordLenBack = 4;  // the length word starts this far before the record's first byte
 
 __host__ __device__ inline uint32_t record_header_bytes(uint32_t hash_len) { return 8 + hash_len; }
+
+// ------------------------------------------------------------------------------ LZ4Block stream
+//
+// Per block "LZ4Block" | token | LE32 compressedLen | LE32 originalLen | LE32 check | payload, with
+// token = method | level; after the last block an end mark: method RAW and three zero ints
+// (LZ4BlockOutputStream.flushBufferedData / finish).  The flag values of a reader's status word
+// are the C-ABI's SDFS_CDC_LZ4_STREAM_*.
+
+constexpr uint32_t kStreamHeaderBytes = SDFS_CDC_LZ4_STREAM_HEADER_BYTES;
+constexpr uint32_t kStreamMagicBytes = 8;
+constexpr uint32_t kStreamTokenAt = 8, kStreamCompressedLenAt = 9, kStreamOriginalLenAt = 13, kStreamCheckAt = 17;
+constexpr uint32_t kStreamLevelBase = 10;           // COMPRESSION_LEVEL_BASE: a block holds up to 1 << (10 + level)
+constexpr uint32_t kStreamCheckMask = 0x0FFFFFFFu;  // StreamingXXHash32.asChecksum keeps 28 bits
+
+// byte k of the magic
+__host__ __device__ inline uint8_t stream_magic_byte(uint32_t k) {
+    constexpr char m[kStreamMagicBytes + 1] = "LZ4Block";
+    return (uint8_t)m[k];
+}
+
+__host__ __device__ inline bool stream_block_size_ok(uint32_t block_size) {
+    return block_size >= SDFS_CDC_LZ4_STREAM_MIN_BLOCK && block_size <= SDFS_CDC_LZ4_STREAM_MAX_BLOCK;
+}
+
+// LZ4BlockOutputStream.compressionLevel: max(0, 32 - numberOfLeadingZeros(blockSize - 1) - 10)
+__host__ __device__ inline uint32_t stream_level(uint32_t block_size) {
+    uint32_t bits = 0;
+    for (uint32_t v = block_size - 1; v; v >>= 1) bits++;
+    return bits > kStreamLevelBase ? bits - kStreamLevelBase : 0;
+}
+
+// the writer's choice: the LZ4 block only when it is shorter than the data
+__host__ __device__ inline bool stream_stores_raw(uint32_t lz4_len, uint32_t original_len) {
+    return lz4_len >= original_len;
+}
+
+__host__ __device__ inline uint64_t stream_blocks_of(uint64_t n, uint32_t block_size) {
+    return (n + block_size - 1) / block_size;
+}
+
+__host__ __device__ inline uint64_t stream_bound(uint64_t n, uint32_t block_size) {
+    return n + (uint64_t)kStreamHeaderBytes * (stream_blocks_of(n, block_size) + 1);
+}
+
+// a data block is a header and at least one payload byte
+__host__ __device__ inline uint64_t stream_max_blocks(uint64_t file_len) { return file_len / (kStreamHeaderBytes + 1) + 1; }
+
+__device__ __forceinline__ uint32_t get_le32(const uint8_t* p) {
+    return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+// byte k of a header (k < 21)
+__device__ __forceinline__ uint8_t stream_header_byte(uint32_t k, uint32_t token, uint32_t compressed_len,
+                                                      uint32_t original_len, uint32_t check) {
+    if (k < kStreamMagicBytes) return stream_magic_byte(k);
+    if (k == kStreamTokenAt) return (uint8_t)token;
+    const uint32_t v = k < kStreamOriginalLenAt ? compressed_len : k < kStreamCheckAt ? original_len : check;
+    return (uint8_t)(v >> (8 * ((k - kStreamCompressedLenAt) & 3)));
+}
+
+// What LZ4BlockInputStream.refill decides from a header it has read whole: 0 = a data block,
+// MAGIC / HEADER = refused; *end_mark = the stream ends here.  Nothing of the payload is looked at.
+__device__ __forceinline__ uint32_t stream_header_check(const uint8_t* h, uint32_t* token, int32_t* compressed_len,
+                                                        int32_t* original_len, uint32_t* check, bool* end_mark) {
+    *end_mark = false;
+    for (uint32_t k = 0; k < kStreamMagicBytes; k++)
+        if (h[k] != stream_magic_byte(k)) return SDFS_CDC_LZ4_STREAM_MAGIC;
+    const uint32_t t = h[kStreamTokenAt], method = t & 0xF0u, level = t & 0x0Fu;
+    const int32_t cl = (int32_t)get_le32(h + kStreamCompressedLenAt), ol = (int32_t)get_le32(h + kStreamOriginalLenAt);
+    const uint32_t ck = get_le32(h + kStreamCheckAt);
+    *token = t;
+    *compressed_len = cl;
+    *original_len = ol;
+    *check = ck;
+    if (method != SDFS_CDC_LZ4_STREAM_RAW && method != SDFS_CDC_LZ4_STREAM_LZ4) return SDFS_CDC_LZ4_STREAM_HEADER;
+    if ((int64_t)ol > ((int64_t)1 << (kStreamLevelBase + level)) || ol < 0 || cl < 0 || (ol == 0) != (cl == 0) ||
+        (method == SDFS_CDC_LZ4_STREAM_RAW && ol != cl))
+        return SDFS_CDC_LZ4_STREAM_HEADER;
+    if (ol == 0) {  // and cl == 0
+        if (ck != 0) return SDFS_CDC_LZ4_STREAM_HEADER;
+        *end_mark = true;
+    }
+    return 0;
+}
 
 }  // namespace
 }  // namespace sdfs

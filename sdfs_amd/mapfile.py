@@ -96,3 +96,39 @@ def truncate(index, m, nbuf: int, slot_len: int, size: int, chunk_length: int, h
     if k < nbuf:
         index.claim_slots(m, nbuf, slot_len, -1, sel=_range_mask(m, nbuf, k, nbuf), hash_len=hash_len, stream=stream)
     return m[: k * slot_len], k
+
+
+def close_map(codec, m, nbuf: int, slot_len: int, stream=None):
+    """``LongByteArrayMap.close`` under ``Main.COMPRESS_METADATA`` (LongByteArrayMap.java:1003-1015):
+    the closed ``GUID.map`` is replaced by ``GUID.map.lz4`` = ``CompressionUtils.compressFile``.  ``codec``
+    is a :class:`sdfs_amd.lz4_stream.HipLz4BlockStream`.  Returns the ``.map.lz4`` image, a uint8
+    tensor on the device cut to the stream's length (one host read, of that length)."""
+    n = nbuf * slot_len
+    out, _, out_lens = codec.compress_files(m, [0], [n], stream=stream)
+    return out[: int(out_lens[0])]
+
+
+def open_map(codec, image, slot_len: int, stream=None):
+    """A ``.map.lz4`` opened (LongByteArrayMap.java:141-154, 172-177, 464-469): expanded by
+    ``CompressionUtils.decompressFile`` before the first slot is read.  Returns ``(m, nbuf)``.  Raises
+    :class:`SdfsCdcError` where ``LZ4BlockInputStream`` throws (naming the flags), and when the decoded
+    length is not a whole number of slots."""
+    from . import _lib
+    from .lz4_stream import flag_names
+
+    if slot_len < 1:
+        raise ValueError("slot_len")
+    out, _, decoded, status, _ = codec.decompress_files(image, [0], [int(image.shape[0])], stream=stream)
+    if status[0]:
+        raise _lib.SdfsCdcError(_lib.EINVAL, f".map.lz4 is corrupted: {flag_names(int(status[0]))}")
+    n = int(decoded[0])
+    if n % slot_len:
+        raise _lib.SdfsCdcError(_lib.EINVAL, f".map.lz4 decodes to {n} bytes: not a whole number of {slot_len}-byte slots")
+    return out[:n], n // slot_len
+
+
+def snapshot_compressed(codec, m, nbuf: int, slot_len: int, stream=None):
+    """``copy(dest, index=false)`` under ``Main.COMPRESS_METADATA`` (LongByteArrayMap.java:897-940; the
+    copy is written as ``dest.lz4``, :937-938): the slots as a ``.map.lz4`` image, not indexed — the
+    copy counts only once it is opened and :func:`index_map` runs over it."""
+    return close_map(codec, m, nbuf, slot_len, stream)
