@@ -42,6 +42,12 @@ uint64_t sdfs_cdc_lz4_bound(uint64_t n);
 int sdfs_cdc_lz4_create(int device, int mode, sdfs_cdc_lz4** out);
 int sdfs_cdc_lz4_destroy(sdfs_cdc_lz4* z);
 
+/* The batch capacity (n_max) from which sdfs_cdc_lz4_compress_device and
+ * sdfs_cdc_lz4_decompress_device choose their lane kernels (one lane per item) beside the wave
+ * kernels: the device's compute units times a tuned constant.  The choice follows the capacity
+ * the caller gives, never *d_count or the data.  0 for a NULL handle. */
+uint64_t sdfs_cdc_lz4_hybrid_min_items(const sdfs_cdc_lz4* z);
+
 /* Device batch.  Chunk i (i < *d_count when d_count != NULL, else i < n_max) is
  * d_data[d_src_off[i] .. + d_src_len[i]) (each < 2 GiB); its LZ4 block (framed != 0: preceded by
  * the big-endian length, the putChunk record) is written at d_out + d_dst_off[i], which must have

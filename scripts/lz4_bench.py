@@ -30,6 +30,7 @@ NBUF = int(os.environ.get("NBUF", "4096"))
 REPS = int(os.environ.get("REPS", "5"))
 THREADS = int(os.environ.get("THREADS", "16"))
 CPU_SECS = float(os.environ.get("CPU_SECS", "8"))
+SAMPLES = int(os.environ.get("SAMPLES", "0"))  # > 0: also time that many single decode launches (A/B spread)
 MODES = [m for m in os.environ.get("MODES", "r123,v19").split(",") if m]
 SETS = [s for s in os.environ.get("SETS", "random,text").split(",") if s]
 L = 262144
@@ -111,12 +112,19 @@ def main():
             torch.cuda.synchronize()
             dms = ev[0].elapsed_time(ev[1]) / REPS
             assert torch.equal(blen, src_len) and torch.equal(back[:nbytes], batch.data[:nbytes])
-            pending.append((ds, mname, mode, n, nbytes, ms, clen, so, sl, dms))
+            samples = []
+            for _ in range(SAMPLES):
+                ev[0].record(s)
+                comp.decompress_device(out, dst_off, dst_len, back, src_off, src_len, blen)
+                ev[1].record(s)
+                torch.cuda.synchronize()
+                samples.append(round(ev[0].elapsed_time(ev[1]), 4))
+            pending.append((ds, mname, mode, n, nbytes, ms, clen, so, sl, (dms, samples)))
             comp.destroy()
     eng.destroy()
     # CPU oracle (C, THREADS pthreads) on a bounded sample of the same chunks -- after every GPU
     # measurement: a 16-thread CPU phase between two GPU timings halves the second one on the box
-    for ds, mname, mode, n, nbytes, ms, clen, so, sl, dms in pending:
+    for ds, mname, mode, n, nbytes, ms, clen, so, sl, (dms, samples) in pending:
         host = hosts[ds]
         rng = np.random.default_rng(2)
         order = rng.permutation(n)
@@ -154,6 +162,7 @@ def main():
             "input_gib": round(nbytes / 2**30, 3), "kernel_ms": round(ms, 3),
             "gibps": round(nbytes / (ms / 1e3) / 2**30, 1), "ratio": round(nbytes / max(clen, 1), 3),
             "decompress_ms": round(dms, 3), "decompress_gibps": round(nbytes / (dms / 1e3) / 2**30, 1),
+            **({"decompress_samples_ms": samples} if samples else {}),
             "cpu_baseline": {"gibps": round(done_bytes / cpu_secs / 2**30, 3), "threads": THREADS,
                              "sample_chunks": int(k), "kind": "port (oracle/lz4_ref.c)"},
             "cpu_liblz4": sys_leg,

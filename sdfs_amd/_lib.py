@@ -277,6 +277,7 @@ SIGNATURES = {
     "sdfs_cdc_lz4_bound": (ctypes.c_uint64, [ctypes.c_uint64]),
     "sdfs_cdc_lz4_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P(_vp)]),
     "sdfs_cdc_lz4_destroy": (ctypes.c_int, [_vp]),
+    "sdfs_cdc_lz4_hybrid_min_items": (ctypes.c_uint64, [_vp]),
     "sdfs_cdc_lz4_compress_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
                                                     ctypes.c_int, _vp]),
     "sdfs_cdc_lz4_plan_records": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64,

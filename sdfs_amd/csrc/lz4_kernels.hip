@@ -28,12 +28,13 @@
 
 #include "../../include/sdfs_lz4.h"
 #include "cdc_internal.h"
+#include "lz4_decode.h"
 #include "stream_order.h"
 
 namespace sdfs {
 namespace {
 
-constexpr uint32_t kMinMatch = 4, kMfLimit = 12, kLastLiterals = 5, kMlMask = 15, kRunMask = 15;
+constexpr uint32_t kMfLimit = 12, kLastLiterals = 5;  // kMinMatch, kMlMask, kRunMask: lz4_decode.h
 constexpr uint32_t kLimit64K = 65536 + kMfLimit - 1;  // below: 16-bit position table
 constexpr uint32_t kMaxDistance = 65535;
 constexpr uint32_t kScrBuckets = 1024;  // same-entry detection among one round's 64 probes
@@ -100,11 +101,7 @@ __device__ __forceinline__ uint32_t g32(const uint8_t* p) {
     __builtin_memcpy(&v, p, 4);
     return v;
 }
-__device__ __forceinline__ uint64_t g64(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
+// g64: lz4_decode.h
 
 // table index of the sequence at p (lz4_ref.c hash_at)
 template <int MODE, typename P>
@@ -542,22 +539,7 @@ struct Lz4DecArgs {
     uint32_t route;  // 0: every block; 1: compressible blocks only (lane kernel); 2: the others
 };
 
-constexpr uint32_t kLz4Corrupt = 0xFFFFFFFFu;
-
-// Routing of the split decode: a block that saved under 1/16 of its bytes (or a raw record) is
-// mostly literal runs, which the wave kernel copies coalesced; the others are short sequences,
-// which one lane per block parses without the wave's per-sequence round trips.
-__device__ __forceinline__ bool dec_lane_class(const uint8_t* in, uint32_t n, uint32_t cap, uint32_t framed) {
-    uint32_t out = cap;
-    if (framed) {
-        if (n < 4) return false;
-        const int32_t nz = (int32_t)((uint32_t)in[0] << 24 | (uint32_t)in[1] << 16 | (uint32_t)in[2] << 8 | in[3]);
-        if (nz <= 0) return false;
-        out = (uint32_t)nz;
-        n -= 4;
-    }
-    return (uint64_t)n * 16 < (uint64_t)out * 15;
-}
+// kLz4Corrupt and the routing of the split decode (dec_lane_class): lz4_decode.h
 
 // Decode one block of n bytes into dst (cap bytes); returns the decoded length or kLz4Corrupt.
 
@@ -668,111 +650,7 @@ __global__ __launch_bounds__(64) void lz4_decompress_kernel(Lz4DecArgs a) {
     }
 }
 
-// One LANE per block (route 1 of the split decode): the serial parse of decompress_block with
-// 8-byte literal and match copies (an overlapping match with offset < 8 byte by byte, which
-// reads only bytes this lane wrote before).  Same corruption checks, never writes past cap.
-__device__ uint32_t decompress_lane(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst,
-                                    uint32_t cap) {
-    uint32_t ip = 0, op = 0;
-    for (;;) {
-        // fast sequence: short literal run (< 15) with its offset inside the next 17 source
-        // bytes and room for 16-byte literal / 8-byte-rounded match writes before cap.  The
-        // over-written bytes past op are rewritten by the following sequences before anything
-        // reads them (a match only reads below its own op).
-        if (ip + 17 <= n && op + 16 <= cap) {
-            const uint64_t w0 = g64(src + ip), l0 = g64(src + ip + 1), l1 = g64(src + ip + 9);
-            const uint32_t token = (uint32_t)w0 & 255u, lit = token >> 4;
-            if (lit < kRunMask) {
-                __builtin_memcpy(dst + op, &l0, 8);
-                __builtin_memcpy(dst + op + 8, &l1, 8);
-                // offset bytes at lit, lit + 1 of the 16 loaded after the token
-                const uint32_t b0 = lit < 8 ? (uint32_t)(l0 >> (8 * lit)) : (uint32_t)(l1 >> (8 * (lit - 8)));
-                const uint32_t b1 = lit + 1 < 8 ? (uint32_t)(l0 >> (8 * (lit + 1))) : (uint32_t)(l1 >> (8 * (lit - 7)));
-                const uint32_t off = (b0 & 255u) | ((b1 & 255u) << 8);
-                op += lit;
-                ip += 3 + lit;
-                if (off == 0 || off > op) return kLz4Corrupt;
-                uint32_t ml = token & kMlMask;
-                if (ml == kMlMask) {
-                    uint32_t b;
-                    do {
-                        if (ip >= n) return kLz4Corrupt;
-                        b = src[ip++];
-                        ml += b;
-                    } while (b == 255);
-                }
-                ml += kMinMatch;
-                if (op + ml > cap) return kLz4Corrupt;
-                uint32_t k = 0;
-                if (off >= 8) {
-                    if (op + ml + 8 <= cap) {  // 8-byte rounded (wild) copy
-                        for (; k < ml; k += 8) {
-                            const uint64_t v = g64(dst + op - off + k);
-                            __builtin_memcpy(dst + op + k, &v, 8);
-                        }
-                        k = ml;
-                    } else {
-                        for (; k + 8 <= ml; k += 8) {
-                            const uint64_t v = g64(dst + op - off + k);
-                            __builtin_memcpy(dst + op + k, &v, 8);
-                        }
-                    }
-                }
-                for (; k < ml; k++) dst[op + k] = dst[op - off + k];
-                op += ml;
-                continue;
-            }
-        }
-        if (ip >= n) return kLz4Corrupt;
-        const uint32_t token = src[ip++];
-        uint32_t lit = token >> 4;
-        if (lit == kRunMask) {
-            uint32_t b;
-            do {
-                if (ip >= n) return kLz4Corrupt;
-                b = src[ip++];
-                lit += b;
-            } while (b == 255);
-        }
-        if (ip + lit > n || op + lit > cap) return kLz4Corrupt;
-        {
-            uint32_t k = 0;
-            for (; k + 8 <= lit; k += 8) {
-                const uint64_t v = g64(src + ip + k);
-                __builtin_memcpy(dst + op + k, &v, 8);
-            }
-            for (; k < lit; k++) dst[op + k] = src[ip + k];
-        }
-        ip += lit;
-        op += lit;
-        if (ip == n) return op;
-        if (ip + 2 > n) return kLz4Corrupt;
-        const uint32_t off = (uint32_t)src[ip] | ((uint32_t)src[ip + 1] << 8);
-        ip += 2;
-        if (off == 0 || off > op) return kLz4Corrupt;
-        uint32_t ml = token & kMlMask;
-        if (ml == kMlMask) {
-            uint32_t b;
-            do {
-                if (ip >= n) return kLz4Corrupt;
-                b = src[ip++];
-                ml += b;
-            } while (b == 255);
-        }
-        ml += kMinMatch;
-        if (op + ml > cap) return kLz4Corrupt;
-        uint32_t k = 0;
-        if (off >= 8) {  // each 8-byte read ends at or before the first byte this step writes
-            for (; k + 8 <= ml; k += 8) {
-                const uint64_t v = g64(dst + op - off + k);
-                __builtin_memcpy(dst + op + k, &v, 8);
-            }
-        }
-        for (; k < ml; k++) dst[op + k] = dst[op - off + k];
-        op += ml;
-    }
-}
-
+// One LANE per block (route 1 of the split decode): decompress_lane, lz4_decode.h
 __global__ __launch_bounds__(256) void lz4_decompress_lane_kernel(Lz4DecArgs a) {
     const uint64_t n_items = a.d_count ? min<uint64_t>(*a.d_count, a.n_max) : a.n_max;
     for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < n_items; c += (uint64_t)gridDim.x * 256) {
@@ -1224,6 +1102,9 @@ struct sdfs_cdc_lz4 {
 
 namespace {
 
+// the batch capacity from which the automatic choice takes the lane kernels (both launchers)
+uint64_t hybrid_min_items(const sdfs_cdc_lz4* z) { return (uint64_t)z->num_cus * kHybridChunksPerCu; }
+
 template <int D, bool PT>
 hipError_t launch_lane_d(int mode, uint32_t grid, const Lz4Args& g, hipStream_t s) {
     if (mode == SDFS_CDC_LZ4_V19)
@@ -1306,7 +1187,7 @@ int launch_compress_impl(sdfs_cdc_lz4* z, const Lz4Args& a0, hipStream_t s) {
     // wave kernel (scripts/probes/lz4_batch_sweep.sh: the hybrid pays from ~50 000 chunks per 256 CUs).
     // n_max bounds a device-count batch, so the choice follows the capacity the caller gives.
     const int lane_mode = z->lane_mode >= 0 ? z->lane_mode
-                                            : (a.n_max >= (uint64_t)z->num_cus * kHybridChunksPerCu ? 2 : 0);
+                                            : (a.n_max >= hybrid_min_items(z) ? 2 : 0);
     uint64_t lgrid = std::min<uint64_t>((a.n_max + 255) / 256, (uint64_t)z->num_cus * z->lane_wg_per_cu);
     if (z->lane_grid > 0) lgrid = std::min<uint64_t>(lgrid, (uint64_t)z->lane_grid);  // tuning: fewer chains
     if (lane_mode == 1 && !lane_tables(z, lgrid * 256, s))
@@ -1375,6 +1256,8 @@ int launch_compress_impl(sdfs_cdc_lz4* z, const Lz4Args& a0, hipStream_t s) {
 extern "C" {
 
 uint64_t sdfs_cdc_lz4_bound(uint64_t n) { return n + n / 255 + 16; }
+
+uint64_t sdfs_cdc_lz4_hybrid_min_items(const sdfs_cdc_lz4* z) { return z ? hybrid_min_items(z) : 0; }
 
 int sdfs_cdc_lz4_create(int device, int mode, sdfs_cdc_lz4** out) {
     if (!out) return fail_status(SDFS_CDC_EINVAL, "null output");
@@ -1558,7 +1441,7 @@ int sdfs_cdc_lz4_decompress_device(sdfs_cdc_lz4* z, const uint8_t* d_src, const 
     std::lock_guard<std::mutex> lk(z->mu);
     LZ_TRY(hipSetDevice(z->device));
     Lz4DecArgs a{d_src, d_src_off, d_src_len, d_count, n_max, d_out, d_dst_off, d_dst_cap, d_dst_len, framed ? 1u : 0u};
-    const bool split = z->dec_split >= 0 ? z->dec_split != 0 : n_max >= (uint64_t)z->num_cus * kHybridChunksPerCu;
+    const bool split = z->dec_split >= 0 ? z->dec_split != 0 : n_max >= hybrid_min_items(z);
     if (split) {  // compressible blocks one lane each, then the rest one wave each (same stream)
         a.route = 1;
         const uint64_t lg = std::min<uint64_t>((n_max + 255) / 256, (uint64_t)z->num_cus * z->dec_lane_wg_per_cu);

@@ -46,6 +46,10 @@ class HipLz4Compressor:
         except Exception:
             pass
 
+    def hybrid_min_items(self) -> int:
+        """Batch capacity from which compress_device / decompress_device take the lane kernels."""
+        return int(self._lib.sdfs_cdc_lz4_hybrid_min_items(self._h))
+
     # ---- LZ4Compressor
     def maxCompressedLength(self, n: int) -> int:
         return int(self._lib.sdfs_cdc_lz4_bound(int(n)))

@@ -288,9 +288,8 @@ def test_gpu_hybrid_batch_with_records_over_128k_vs_oracle():
     """A hybrid-size batch (>= 192 chunks per CU, so lanes compress the compressible chunks) that
     also holds compressible records of 128 KiB + 1 .. 1 MiB: a lane's table entry keeps positions
     in 17 bits, so those must go to the wave kernel; every record equals the oracle's."""
-    torch = pytest.importorskip("torch")
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    n_small = 192 * ncu + 64
+    pytest.importorskip("torch")
+    n_small = comp(Z.R123).hybrid_min_items() + 64
     rng = np.random.default_rng(128)
     src = Z.text_like(1, 91, 8 << 20)
     longs = [131072, 131073, 200000, 262144, 524288 + 17, 1 << 20]
@@ -337,7 +336,7 @@ def test_gpu_large_batch_hybrid_vs_oracle():
     batch.run()
     recs = batch.record_table()
     n = int(recs.shape[0])
-    assert n >= 192 * torch.cuda.get_device_properties(0).multi_processor_count
+    assert n >= comp(Z.R123).hybrid_min_items()
     host = batch.data.cpu().numpy()
     for mode in (Z.R123, Z.V19):
         c = comp(mode)
@@ -408,3 +407,99 @@ def test_gpu_literal_screen_edges_vs_oracle(mode):
     got = comp(mode).compress_chunks(base, offs, lens, framed=True)
     for i, p in enumerate(parts):
         assert got[i] == Z.compress_framed(p, mode), (i, len(p), i % 5)
+
+
+HYBRID_LENS = [0, 1, 4, 5, 12, 13, 14, 64, 65546, 65547, 65548, 131071, 131072, 131073]
+
+
+def _planted(rng, n, kind, stream):
+    """The five kinds of the literal-screen test: random; a word planted again further on;
+    position 0's word again; a zero word or two; random again."""
+    d = bytearray(C.synth(9, stream, 0, n).tobytes())
+    if kind == 1 and n > 40:
+        a = int(rng.integers(0, n // 2))
+        b = int(rng.integers(a + 4, n - 4))
+        d[b:b + 4] = d[a:a + 4]
+    elif kind == 2 and n > 40:
+        b = int(rng.integers(1, n - 4))
+        d[b:b + 4] = d[0:4]
+    elif kind == 3 and n > 40:
+        for _ in range(int(rng.integers(1, 3))):
+            b = int(rng.integers(0, n - 4))
+            d[b:b + 4] = b"\0\0\0\0"
+    return bytes(d)
+
+
+_EDGE_BATCH = {}
+
+
+def _hybrid_edge_batch(salt):
+    """The edge lengths across KINDS and the planted-word kinds, all-zero chunks and chunks of
+    period 1 .. 9; `salt` changes the data and keeps the shape.  Built once per salt."""
+    if salt in _EDGE_BATCH:
+        return _EDGE_BATCH[salt]
+    rng = np.random.default_rng(77 + salt)
+    parts = []
+    for li, n in enumerate(HYBRID_LENS):
+        parts += [_gen(kind, n, stream=4000 + 1000 * salt + 8 * li + ki) for ki, kind in enumerate(KINDS)]
+        parts += [_planted(rng, n, pk, 6000 + 1000 * salt + 8 * li + pk) for pk in range(5)]
+        parts.append(bytes(n))
+    for per in range(1, 10):
+        pat = bytes(rng.integers(0, 256, per, dtype=np.uint8))
+        parts += [(pat * (n // per + 1))[:n] for n in (13, 14, 64, 65547, 131073)]
+    _EDGE_BATCH[salt] = parts
+    return parts
+
+
+def _compress_on_the_hybrid_route(c, parts, mode):
+    """compress_device with arrays padded to the hybrid threshold and count = K: the records, after
+    checking each against the oracle's and that nothing past the count was written."""
+    import torch
+
+    thr = c.hybrid_min_items()
+    K = len(parts)
+    assert 0 < K < thr
+    lens = np.array([len(p) for p in parts], np.uint32)
+    offs = np.concatenate([[0], np.cumsum(lens[:-1].astype(np.uint64) + 3)]).astype(np.uint64)  # unaligned
+    base = np.zeros(int(offs[-1]) + int(lens[-1]) + 16, np.uint8)
+    for o, p in zip(offs, parts):
+        base[int(o): int(o) + len(p)] = np.frombuffer(p, np.uint8)
+    room = lens.astype(np.int64) + lens // 255 + 20
+    dst_off = np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.int64)
+    dev = torch.device("cuda:0")
+
+    def padded(a, dt):
+        t = torch.zeros(thr, dtype=dt, device=dev)
+        t[:K] = torch.from_numpy(np.ascontiguousarray(a).astype(np.int64)).to(dev, dt)
+        return t
+
+    out = torch.full((int(room.sum()) + 16,), 0xA5, dtype=torch.uint8, device=dev)
+    dst_len = torch.full((thr,), 0x5EA5EA5, dtype=torch.int32, device=dev)
+    src_len = padded(lens, torch.int32)
+    assert src_len.shape[0] >= c.hybrid_min_items()  # the capacity that selects the lane kernels
+    c.compress_device(torch.from_numpy(base).to(dev), padded(offs, torch.int64), src_len, out,
+                      padded(dst_off, torch.int64), dst_len, count=torch.tensor([K], dtype=torch.int32, device=dev))
+    torch.cuda.synchronize()
+    o, dl = out.cpu().numpy(), dst_len.cpu().numpy()
+    assert (dl[K:] == 0x5EA5EA5).all()
+    got = [o[int(a): int(a) + int(k)].tobytes() for a, k in zip(dst_off, dl[:K])]
+    want, _ = Z.compress_batch(base, offs, lens, mode, 16)
+    bad = [(i, int(lens[i])) for i in range(K) if got[i] != want[i]]
+    assert not bad, (mode, len(bad), bad[:8])
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [Z.R123, Z.V19], ids=["r123", "v19"])
+def test_gpu_hybrid_route_edge_lengths_and_table_reuse_vs_oracle(mode):
+    """The lane kernel and its bail list on the lengths where the parse changes (no search below
+    13 bytes, the 64 KiB + 11 table switch, the 128 KiB limit of a lane's table entries), on the
+    literal screen's planted words, zero words and short periods: every record equals the
+    oracle's.  Then another batch of the same shape on the same lane tables, then the first
+    again: a table entry of an earlier generation must read as position 0, so every run equals
+    the oracle's and the third equals the first byte for byte."""
+    c = comp(mode)
+    first = _compress_on_the_hybrid_route(c, _hybrid_edge_batch(0), mode)
+    _compress_on_the_hybrid_route(c, _hybrid_edge_batch(1), mode)
+    again = _compress_on_the_hybrid_route(c, _hybrid_edge_batch(0), mode)
+    assert again == first

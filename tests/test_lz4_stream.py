@@ -290,9 +290,9 @@ def capi_compress(codec, files, B):
     return [host[int(o): int(o) + int(k)].tobytes() for o, k in zip(out_offs, got_lens)]
 
 
-def capi_read(codec, streams, exact_blocks=True):
+def capi_read(codec, streams, exact_blocks=True, info=None):
     """scan + decompress through the C-ABI with canaries around every decoded extent.  Returns per
-    file (walk dict, final status, decoded bytes)."""
+    file (walk dict, final status, decoded bytes); info (a dict) receives the block bound passed."""
     torch = _torch()
     lib = _lib.load()
     img, offs, lens = _lay(streams)
@@ -320,9 +320,12 @@ def capi_read(codec, streams, exact_blocks=True):
     out_img, out_offs, _ = _lay([bytes(int(k)) for k in decoded], step=1)
     out = torch.full((len(out_img),), CANARY, dtype=torch.uint8, device="cuda")
     total = sum(w["n_blocks"] for w in walks)
+    max_blocks = total if exact_blocks else int(cap.sum())
+    if info is not None:
+        info["max_blocks"] = max_blocks
     _lib.check(lib.sdfs_cdc_lz4_stream_decompress_device(
         codec.z._h, d.data_ptr(), n, files.data_ptr(), blocks.data_ptr(), base.ctypes.data,
-        total if exact_blocks else int(cap.sum()), out.data_ptr(), out_offs.ctypes.data, decoded.ctypes.data, s))
+        max_blocks, out.data_ptr(), out_offs.ctypes.data, decoded.ctypes.data, s))
     f2 = files.cpu().numpy().view(np.uint64)
     host = out.cpu().numpy()
     assert (d.cpu().numpy() == img).all()
@@ -460,6 +463,47 @@ def test_gpu_round_trip_map_and_host_bytes():
     streams = [M.write(_gen(k, 3000, 30 + i), 1024) for i, k in enumerate(KINDS)]
     for (walk, status, data), k in zip(capi_read(codec, streams, exact_blocks=False), KINDS):
         assert status == 0 and data == _gen(k, 3000, 30 + KINDS.index(k))
+
+
+@pytest.mark.gpu
+def test_gpu_reader_on_the_split_route():
+    """The reader passes its block bound to the LZ4 decode as the batch capacity, and the decode
+    chooses its route by capacity: with the bound the C-ABI documents (the sum of
+    stream_max_blocks = len / 22 + 1) a batch above ~1.08 MB of streams takes the split decode
+    with bare 64 KiB blocks, with the exact block count it takes the wave kernel.  Text files,
+    64 KiB random files (RAW blocks: zero-length entries in the decode batch) and every
+    corruption beside good neighbours: statuses, walks and bytes equal the model on both."""
+    codec = _codec()
+    lib = _lib.load()
+    thr = int(lib.sdfs_cdc_lz4_hybrid_min_items(codec.z._h))
+    assert thr > 0
+    texts = [M.write(_gen("text", n, 910 + i), B)
+             for i, (n, B) in enumerate(((5000, 1024), (70000, 65536), (300, 64), (20000, 65536)))]
+    rnd = [M.write(_gen("rand", 65536, 920 + i), 65536) for i in range(2)]
+    streams = []
+    for i, name in enumerate(sorted(CORRUPTIONS)):
+        streams += [texts[i % 4], CORRUPTIONS[name][0]]
+    streams += texts
+    i = 0
+    while sum(len(s) // 22 + 1 for s in streams) < thr + 1:
+        streams.append(rnd[i % 2])
+        i += 1
+    assert sum(len(s) for s in streams) > 22 * thr and i >= 4
+    split, wave = {}, {}
+    res_split = capi_read(codec, streams, exact_blocks=False, info=split)
+    res_wave = capi_read(codec, streams, exact_blocks=True, info=wave)
+    assert split["max_blocks"] >= thr > wave["max_blocks"] > 0, (split, wave, thr)
+    model = {}
+    for i, s in enumerate(streams):
+        m = model.setdefault(s, M.read(s))
+        for route, res in (("split", res_split), ("wave", res_wave)):
+            walk, status, data = res[i]
+            assert M.flag_names(status) == M.flag_names(m["status"]), (route, i)
+            assert _same_walk(walk, m), (route, i)
+            if m["status"] == 0:
+                assert data == m["data"], (route, i)
+        assert res_split[i][:2] == res_wave[i][:2], i
+    assert sum(model[s]["status"] != 0 for s in streams) >= 15
 
 
 @pytest.mark.gpu
