@@ -16,6 +16,19 @@
  *     sdfs_cdc_read_assemble    per-buffer status, then the gather of the pieces into the buffers
  *     sdfs_cdc_read_verify      Main.VERIFY_READS: re-hash the chunks, report mismatches
  *
+ * Ranged reads — DedupFileChannel.read(buf, bufPos, siz, filePos) (DedupFileChannel.java:499-608)
+ * for a batch of byte ranges over several files — use the same parse, decrypt, decode and verify
+ * and three entry points of their own:
+ *
+ *     sdfs_cdc_read_split           host: requests -> n_read, pieces cut at buffer boundaries, and
+ *                                   the rows (the distinct touched slots; only these are parsed)
+ *     sdfs_cdc_read_plan_pieces     the records the pairs touched by some piece need, each once
+ *     sdfs_cdc_read_assemble_pieces per-piece status, then the gather of the ragged pieces
+ *
+ * One divergence from the reference, on purpose: WritableCacheBuffer.readChunk rebuilds the whole
+ * buffer, so a bad record anywhere in it fails every read of that buffer; a ranged read here is
+ * decided by the pairs that touch the range alone (see sdfs_cdc_read_plan_pieces).
+ *
  * hashloc is the fingerprint's pos of sdfs_cdc_index_put_records (sdfs_index.h): pos_base + the
  * rank of the insertion.  The host owns the chunk store and hands in a directory indexed by
  * hashloc - pos_base.  Errors, threading, the thread-local sdfs_cdc_last_error() message and the
@@ -138,6 +151,89 @@ int sdfs_cdc_read_verify(sdfs_cdc_engine* engine, uint32_t nbuf, const sdfs_cdc_
                          const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
                          const uint32_t* d_fetch_len, const uint32_t* d_fetch_count, uint64_t n_fetch_max,
                          uint8_t* d_pair_bad, uint32_t* d_bad_count, void* stream);
+
+/* ---- ranged reads -------------------------------------------------------------------------- */
+
+/* A file of one map image: its slots are rows first_slot .. first_slot + n_slots of the image; it
+ * is file_len bytes long (a sparse file may be longer than n_slots * chunk_length). */
+typedef struct sdfs_cdc_read_file {
+    uint64_t first_slot;
+    uint64_t n_slots;
+    uint64_t file_len;
+} sdfs_cdc_read_file;
+
+/* DedupFileChannel.read(buf, bufPos = out_off, siz, filePos = file_pos) on files[file]. */
+typedef struct sdfs_cdc_read_request {
+    uint64_t file;
+    uint64_t file_pos;
+    uint64_t siz;
+    uint64_t out_off;
+} sdfs_cdc_read_request;
+
+/* The request layer (DedupFileChannel.java:499-608, WritableCacheBuffer.readChunk :217-245), on the
+ * host, all arrays host memory.  Request r: file_pos >= file_len -> n_read[r] = -1, no pieces;
+ * else n_read[r] = min(siz, file_len - file_pos) (siz == 0 -> 0) and [file_pos, file_pos + n_read)
+ * is cut at multiples of chunk_length into pieces, in request order then ascending position:
+ * piece_req = r, piece_start = pos % chunk_length, piece_len, piece_out_off following each other
+ * from the request's out_off, and piece_row = the index in row_slot of the slot first_slot + pos /
+ * chunk_length — SDFS_CDC_READ_NONE when pos / chunk_length >= n_slots (the map is shorter than
+ * the file: the reference hands out a blank buffer, the piece reads as zeros with status 0).
+ * row_slot[0 .. *n_rows) = the distinct touched slots, ascending.
+ * *n_pieces / *n_rows are always the needed counts; SDFS_CDC_ECAP when piece_cap or row_cap is
+ * smaller (nothing else is written then).  Bounds: pieces <= sum over requests of (siz /
+ * chunk_length + 2), rows <= pieces.  64-bit position arithmetic, checked: a file index >=
+ * n_files, first_slot + n_slots, out_off + n_read or siz > INT64_MAX overflowing, or more than
+ * UINT32_MAX - 1 pieces are SDFS_CDC_EINVAL. */
+int sdfs_cdc_read_split(const sdfs_cdc_read_file* files, uint32_t n_files, const sdfs_cdc_read_request* requests,
+                        uint32_t n_requests, uint32_t chunk_length, int64_t* n_read, uint32_t piece_cap,
+                        uint32_t* piece_req, uint32_t* piece_row, uint32_t* piece_start, uint32_t* piece_len,
+                        uint64_t* piece_out_off, uint32_t row_cap, uint64_t* row_slot, uint64_t* n_pieces,
+                        uint64_t* n_rows);
+
+/* sdfs_cdc_read_plan for pieces: pairs holds the nbuf parsed rows; piece p reads [d_piece_start[p],
+ * + d_piece_len[p]) of row d_piece_row[p] (SDFS_CDC_READ_NONE or >= nbuf: no row, zeros; start +
+ * len <= chunk_length is the caller's to keep).  With U = the row's pairs in ascending pos up to,
+ * not including, the first hashloc == 0, a pair of U touches the piece iff nlen > 0, pos < start +
+ * len and pos + nlen > start (c = min(nlen, ck.length) <= nlen: a pair that does not touch cannot
+ * supply a byte of the piece).  d_piece_status[p] = SDFS_CDC_READ_CORRUPT when the row did not
+ * parse, else SDFS_CDC_READ_MISSING when a touching pair's hashloc is outside the directory, else
+ * 0.  A pair is needed iff it touches a piece whose status here is 0; the fetch list is the
+ * distinct directory entries of the needed pairs, laid out exactly as sdfs_cdc_read_plan lays out
+ * its own.  d_pair_fetch is written for every slot of every row and is SDFS_CDC_READ_NONE for a
+ * pair nobody needs — the used pairs are no prefix of the row here.  pairs->status is not written.
+ * Divergence from the reference (which rebuilds the whole buffer): a missing, failed or misplaced
+ * pair fails only the pieces it touches; whenever the whole-buffer read of a row has status 0 the
+ * ranged bytes equal the slice of that buffer. */
+int sdfs_cdc_read_plan_pieces(int device, uint32_t nbuf, const sdfs_cdc_pairs* pairs, uint64_t pos_base,
+                              uint64_t n_store, const uint64_t* d_store_off, const uint32_t* d_store_len,
+                              const uint32_t* d_store_raw_len, uint32_t n_pieces, const uint32_t* d_piece_row,
+                              const uint32_t* d_piece_start, const uint32_t* d_piece_len, uint32_t* d_piece_status,
+                              uint32_t* d_pair_fetch, uint32_t* d_fetch_count, uint64_t* d_src_off, uint32_t* d_src_len,
+                              uint64_t* d_dst_off, uint32_t* d_dst_cap, uint64_t* d_plain_off, uint64_t* d_total_bytes,
+                              void* stream);
+
+/* WritableCacheBuffer.readChunk (:217-245: initBuffer, then arraycopy of [startPos, startPos + len))
+ * for n_pieces pieces: piece p = d_out[d_piece_out_off[p] .. + d_piece_len[p]), every byte written
+ * exactly once, no byte outside the pieces' extents written, any alignment; overlapping extents are
+ * the caller's error.  d_piece_status is in/out: a piece whose status is still 0 gets
+ * SDFS_CDC_READ_FETCH when a touching pair's fetch failed, else SDFS_CDC_READ_BOUNDS when a
+ * touching pair breaks one of sdfs_cdc_read_assemble's three placement conditions.  A piece with
+ * status 0 gets, per byte, the value of the last needed pair in pos order that covers it, else
+ * zero; any other piece, and a piece without a row, is all zeros.
+ * d_req_status (optional, with d_piece_req: piece p belongs to request d_piece_req[p] < n_requests):
+ * d_req_status[r] = the OR of the final statuses of request r's pieces, 0 for a request without
+ * pieces; all n_requests entries are written.
+ * The gather's work units are 64 KiB tiles of the pieces.  A tile stages in LDS only the piece's
+ * window of pairs — from the first pair whose running max of end exceeds start to the last with
+ * pos < start + len — so the LDS form applies whenever the window holds at most 1024 pairs,
+ * whatever pairs->cap is; a larger window is searched in global memory. */
+int sdfs_cdc_read_assemble_pieces(int device, uint32_t nbuf, uint32_t chunk_length, const sdfs_cdc_pairs* pairs,
+                                  const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
+                                  const uint32_t* d_fetch_len, uint32_t n_pieces, const uint32_t* d_piece_row,
+                                  const uint32_t* d_piece_start, const uint32_t* d_piece_len,
+                                  const uint64_t* d_piece_out_off, uint32_t* d_piece_status,
+                                  const uint32_t* d_piece_req, uint32_t n_requests, uint32_t* d_req_status,
+                                  uint8_t* d_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ from .engine import (  # noqa: F401
     SdfsConfig,
 )
 from .archive import ArchiveSet, HipBlobArchiver, HipBufferWriter  # noqa: F401
-from .read import HipBufferReader, parse_map_slots  # noqa: F401
+from .read import HipBufferReader, assemble_pieces, parse_map_slots, plan_pieces, split_requests  # noqa: F401
 from .store import lookup, open_store, scan_store, scrub  # noqa: F401
 from .extent import copy_extents, rewrite_blocks, split_extent  # noqa: F401
 from .mapfile import close_map, index_map, open_map, snapshot, snapshot_compressed, trim, truncate, vanish  # noqa: F401
@@ -27,6 +27,7 @@ __all__ = [
     "index_map", "snapshot", "vanish", "trim", "truncate", "close_map", "open_map", "snapshot_compressed",
     "HipLz4BlockStream", "compressFile", "decompressFile", "xxh32",
     "ArchiveSet", "HipBlobArchiver", "HipBufferWriter", "HipBufferReader", "parse_map_slots",
+    "split_requests", "plan_pieces", "assemble_pieces",
     "open_store", "scan_store", "lookup", "scrub", "copy_extents", "rewrite_blocks", "split_extent",
     "Finger", "HashFunctionPool", "HipVariableMD5HashEngine", "HipVariableSha256HashEngine", "SdfsConfig",
     "SdfsCdcError", "POLY", "VARIABLE_MD5", "VARIABLE_SHA256", "VARIABLE_SHA256_160",

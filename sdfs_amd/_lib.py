@@ -316,6 +316,15 @@ SIGNATURES = {
                                               _vp, _vp, _vp, _vp]),
     "sdfs_cdc_read_verify": (ctypes.c_int, [_vp, ctypes.c_uint32, _P(Pairs), ctypes.c_uint32, _vp, _vp, _vp, _vp,
                                             _vp, ctypes.c_uint64, _vp, _vp, _vp]),
+    "sdfs_cdc_read_split": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                           ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _u64p,
+                                           _u64p]),
+    "sdfs_cdc_read_plan_pieces": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _P(Pairs), ctypes.c_uint64,
+                                                 ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_read_assemble_pieces": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _P(Pairs), _vp,
+                                                     _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     ctypes.c_uint32, _vp, _vp, _vp]),
     # include/sdfs_archive.h
     "sdfs_cdc_archive_map_size": (ctypes.c_uint32, [ctypes.c_uint64]),
     "sdfs_cdc_archive_pack_span": (ctypes.c_uint32, []),

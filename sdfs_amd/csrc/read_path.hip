@@ -22,6 +22,12 @@
 //   - else byte by byte: per byte the floor entry, then back to the last earlier pair that reaches
 //     the byte (the overlap rule; the walk ends where the running max of end stops reaching it).
 // The first and last vectors of a buffer whose ends are not 16-byte aligned are stored bytewise.
+//
+// Ranged reads (DedupFileChannel.read, DedupFileChannel.java:499-608; the "pieces" section below):
+// the host split (read_split.h) cuts requests into pieces {row, start, len, out_off}; the plan marks
+// only the directory entries of the pairs that touch a piece; the same tile body gathers ragged,
+// arbitrarily aligned pieces, its work list built from a prefix over the pieces' tile counts, and
+// stages only the piece's window of pairs in LDS.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +37,7 @@
 #include "../../include/sdfs_read.h"
 #include "block_scan.h"
 #include "call_support.h"
+#include "read_split.h"
 #include "store_format.h"
 
 namespace sdfs {
@@ -40,8 +47,13 @@ constexpr uint32_t kNone = SDFS_CDC_READ_NONE;
 constexpr int kGatherThreads = 256;
 constexpr uint32_t kTileVecs = 4096;  // 16-byte vectors per workgroup (64 KiB): 4 groups of 4 per lane
 constexpr uint32_t kLdsPairs = 1024;  // used pairs per buffer staged in LDS (20 KiB)
+// workgroups of the pieces' gather at most (they stride over the tiles): about one tile each up to
+// 4 GiB of output for the LDS form; the global-memory form is the rare one
+constexpr uint32_t kPieceGrid = 65536, kPieceGridBig = 4096;
 
 __device__ __forceinline__ bool wave_any(bool v) { return __ballot(v) != 0; }
+// a value every lane of the wave holds alike, moved to a scalar register
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // ---------------------------------------------------------------------------------------- parse
 
@@ -348,35 +360,16 @@ __device__ __forceinline__ uint8_t gather_byte(const PairView& v, const uint8_t*
     return 0;
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
-    __shared__ int32_t s_pos[LDS ? kLdsPairs : 1], s_end[LDS ? kLdsPairs : 1], s_max[LDS ? kLdsPairs : 1];
-    __shared__ uint64_t s_src[LDS ? kLdsPairs : 1];
-    const uint32_t b = blockIdx.x / a.tiles_per_buf;
-    const uint32_t tile = blockIdx.x % a.tiles_per_buf;
-    const uint32_t tid = threadIdx.x;
-    const int64_t cl = a.chunk_length;
-    uint8_t* ob = a.out + (uint64_t)b * a.chunk_length;
-    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(ob) & 15);
-    const uint64_t nvec = ((uint64_t)head + a.chunk_length + 15) / 16;  // vectors at absolute 16-byte addresses
-    const uint64_t v0 = (uint64_t)tile * kTileVecs;
-    if (v0 >= nvec) return;  // uniform over the workgroup
-    const uint64_t base = (uint64_t)b * a.p.cap;
-    PairView pv{a.p.pos + base, a.end + base, a.maxend + base, a.src + base, (int32_t)a.nused[b]};
-    if (LDS) {
-        if (pv.n > (int32_t)kLdsPairs) pv.n = 0;  // not reached: the host picks the global form above kLdsPairs
-        for (int32_t i = tid; i < pv.n; i += kGatherThreads) {
-            s_pos[i] = pv.pos[i];
-            s_end[i] = pv.end[i];
-            s_max[i] = pv.maxend[i];
-            s_src[i] = pv.src[i];
-        }
-        __syncthreads();
-        pv.pos = s_pos;
-        pv.end = s_end;
-        pv.maxend = s_max;
-        pv.src = s_src;
-    }
+// One 64 KiB tile (kTileVecs vectors from v0) of the bytes [start, start + len) of a buffer, which
+// go to ob[0 .. len): the whole buffer (start 0, len chunk_length) for gather_kernel, a piece of
+// one for gather_pieces_kernel.  pv holds the pairs that can supply a byte of the range; head =
+// ob & 15 and nvec = the range's vectors at absolute 16-byte addresses (range_vecs), v0 < nvec.
+__device__ __forceinline__ uint64_t range_vecs(uint32_t head, uint32_t len) { return ((uint64_t)head + len + 15) / 16; }
+
+template <bool WHOLE>  // WHOLE: the range is the buffer, start = 0
+__device__ __forceinline__ void gather_tile(const PairView& pv, const uint8_t* chunks, uint8_t* ob, int64_t start_,
+                                            int64_t len, uint32_t head, uint64_t nvec, uint64_t v0, uint32_t tid) {
+    const int64_t start = WHOLE ? 0 : start_;
     // per group of kIt vectors a lane makes three passes, so that the source loads of all of them
     // are in flight together: classify, load, realign + store
     constexpr int kIt = 4;
@@ -395,18 +388,19 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
         sa[it] = 0;
         const uint64_t v = w0 + (uint64_t)it * kGatherThreads;
         if (v >= nvec) continue;
-        const int64_t o = (int64_t)v * 16 - head;  // buffer offset of the vector's first byte
-        const int32_t x0 = (int32_t)max<int64_t>(o, 0);
+        const int64_t r = (int64_t)v * 16 - head;  // offset in the range of the vector's first byte
+        const int64_t o = start + r;               // its buffer offset
+        const int32_t x0 = (int32_t)max<int64_t>(o, start);
         k = floor_index(pv.pos, pv.n, x0, k);  // the largest pos <= x0
         kf[it] = k;
-        if (o < 0 || o + 16 > cl) {  // a buffer end that is not 16-byte aligned
+        if (r < 0 || r + 16 > len) {  // an end of the range that is not 16-byte aligned
             mode[it] = kEdge;
             continue;
         }
         const int64_t next = k + 1 < pv.n ? pv.pos[k + 1] : INT64_MAX;
         if (next >= o + 16 && k >= 0 && pv.end[k] >= o + 16) {
             mode[it] = kCopy;
-            sa[it] = reinterpret_cast<uintptr_t>(a.chunks + pv.src[k] + (uint64_t)(x0 - pv.pos[k]));
+            sa[it] = reinterpret_cast<uintptr_t>(chunks + pv.src[k] + (uint64_t)(x0 - pv.pos[k]));
         } else if (next >= o + 16 && (k < 0 || pv.maxend[k] <= o)) {
             mode[it] = kZero;
         } else {
@@ -427,29 +421,28 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
     for (int it = 0; it < kIt; it++) {
         if (mode[it] == kSkip) continue;
         const uint64_t v = w0 + (uint64_t)it * kGatherThreads;
-        const int64_t o = (int64_t)v * 16 - head;
-        uint8_t* dst = ob + o;
+        const int64_t r = (int64_t)v * 16 - head;
+        const int64_t o = start + r;
+        uint8_t* dst = ob + r;
         int32_t kk = kf[it];
         if (mode[it] == kEdge) {
-            for (int j = 0; j < 16; j++) {
-                const int64_t x = o + j;
-                if (x >= 0 && x < cl) dst[j] = gather_byte(pv, a.chunks, (int32_t)x, kk);
-            }
+            for (int j = 0; j < 16; j++)
+                if (r + j >= 0 && r + j < len) dst[j] = gather_byte(pv, chunks, (int32_t)(o + j), kk);
             continue;
         }
         uint4 w = make_uint4(0, 0, 0, 0);
         if (mode[it] == kCopy) {
-            const uint32_t sh = (uint32_t)(sa[it] & 15), q = sh >> 2, r = sh & 3;
+            const uint32_t sh = (uint32_t)(sa[it] & 15), q = sh >> 2, rb = sh & 3;
             const uint4 l = lo[it], h = hi[it];
             uint32_t t0, t1, t2, t3, t4;
             if (q == 0) { t0 = l.x; t1 = l.y; t2 = l.z; t3 = l.w; t4 = h.x; }
             else if (q == 1) { t0 = l.y; t1 = l.z; t2 = l.w; t3 = h.x; t4 = h.y; }
             else if (q == 2) { t0 = l.z; t1 = l.w; t2 = h.x; t3 = h.y; t4 = h.z; }
             else { t0 = l.w; t1 = h.x; t2 = h.y; t3 = h.z; t4 = h.w; }
-            w.x = __builtin_amdgcn_alignbyte(t1, t0, r);
-            w.y = __builtin_amdgcn_alignbyte(t2, t1, r);
-            w.z = __builtin_amdgcn_alignbyte(t3, t2, r);
-            w.w = __builtin_amdgcn_alignbyte(t4, t3, r);
+            w.x = __builtin_amdgcn_alignbyte(t1, t0, rb);
+            w.y = __builtin_amdgcn_alignbyte(t2, t1, rb);
+            w.z = __builtin_amdgcn_alignbyte(t3, t2, rb);
+            w.w = __builtin_amdgcn_alignbyte(t4, t3, rb);
         } else if (mode[it] == kBytes) {
             uint32_t ws[4];
 #pragma unroll
@@ -457,13 +450,269 @@ __global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
                 uint32_t word = 0;
 #pragma unroll
                 for (int bb = 0; bb < 4; bb++)
-                    word |= (uint32_t)gather_byte(pv, a.chunks, (int32_t)o + 4 * j + bb, kk) << (8 * bb);
+                    word |= (uint32_t)gather_byte(pv, chunks, (int32_t)o + 4 * j + bb, kk) << (8 * bb);
                 ws[j] = word;
             }
             w = make_uint4(ws[0], ws[1], ws[2], ws[3]);
         }
         *reinterpret_cast<uint4*>(dst) = w;
     }
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kGatherThreads) void gather_kernel(AsmArgs a) {
+    __shared__ int32_t s_pos[LDS ? kLdsPairs : 1], s_end[LDS ? kLdsPairs : 1], s_max[LDS ? kLdsPairs : 1];
+    __shared__ uint64_t s_src[LDS ? kLdsPairs : 1];
+    const uint32_t b = blockIdx.x / a.tiles_per_buf;
+    const uint32_t tile = blockIdx.x % a.tiles_per_buf;
+    const uint32_t tid = threadIdx.x;
+    uint8_t* ob = a.out + (uint64_t)b * a.chunk_length;
+    const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(ob) & 15);
+    const uint64_t nvec = range_vecs(head, a.chunk_length);
+    const uint64_t v0 = (uint64_t)tile * kTileVecs;
+    if (v0 >= nvec) return;  // uniform over the workgroup
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    PairView pv{a.p.pos + base, a.end + base, a.maxend + base, a.src + base, (int32_t)a.nused[b]};
+    if (LDS) {
+        if (pv.n > (int32_t)kLdsPairs) pv.n = 0;  // not reached: the host picks the global form above kLdsPairs
+        for (int32_t i = tid; i < pv.n; i += kGatherThreads) {
+            s_pos[i] = pv.pos[i];
+            s_end[i] = pv.end[i];
+            s_max[i] = pv.maxend[i];
+            s_src[i] = pv.src[i];
+        }
+        __syncthreads();
+        pv.pos = s_pos;
+        pv.end = s_end;
+        pv.maxend = s_max;
+        pv.src = s_src;
+    }
+    gather_tile<true>(pv, a.chunks, ob, 0, a.chunk_length, head, nvec, v0, tid);
+}
+
+// ---------------------------------------------------------------------------------------- pieces
+// Ranged reads (sdfs_cdc_read_plan_pieces / sdfs_cdc_read_assemble_pieces): the unit is a piece
+// {row, start, len, out_off}, a byte range of one buffer.  Only the pairs that touch a piece (nlen
+// > 0, pos < start + len, pos + nlen > start) decide its status and are fetched.
+
+struct PieceArgs {
+    uint32_t nbuf;  // rows in the pairs
+    uint32_t n_pieces;
+    const uint32_t* row;  // >= nbuf (SDFS_CDC_READ_NONE): no row, the piece reads as zeros
+    const uint32_t* start;
+    const uint32_t* len;
+    const uint64_t* out_off;  // assemble only
+    uint32_t* status;
+    const uint32_t* req;   // assemble only, optional: the piece's request,
+    uint32_t n_requests;
+    uint32_t* req_status;  // whose status is the OR of its pieces'
+};
+
+// the first i < n with key[i] >= x (key ascending), n if none
+__device__ __forceinline__ uint32_t first_at_least(const int32_t* key, uint32_t n, int64_t x) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (key[mid] >= x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ uint32_t row_pairs(const sdfs_cdc_pairs& p, uint32_t b) {
+    return (p.status[b] & SDFS_CDC_READ_CORRUPT) ? 0 : min(p.counts[b], p.cap);
+}
+
+// pairs before the first hashloc == 0 (the terminator rule), the same for every lane
+__device__ __forceinline__ uint32_t row_used(const sdfs_cdc_pairs& p, uint64_t base, uint32_t n, uint32_t lane) {
+    uint32_t used = n;
+    for (uint32_t i = lane; i < n; i += 64)
+        if (p.hashloc[base + i] == 0) used = min(used, i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) used = min(used, (uint32_t)__shfl_xor(used, o));
+    return used;
+}
+
+// one wave per row: the terminator, and "nobody needs it" for every slot
+__global__ __launch_bounds__(64) void plan_rows_kernel(PlanArgs a, uint32_t* used) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    const uint32_t u = row_used(a.p, base, row_pairs(a.p, b), lane);
+    for (uint32_t i = lane; i < a.p.cap; i += 64) a.pair_fetch[base + i] = kNone;
+    if (lane == 0) used[b] = u;
+}
+
+// one wave per piece: CORRUPT / MISSING, then the directory entries of its touching pairs.
+// Pieces that touch the same pair, or pairs of the same entry, store the same values.
+__global__ __launch_bounds__(64) void plan_mark_pieces_kernel(PlanArgs a, PieceArgs q, const uint32_t* used) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t p = blockIdx.x;
+    const uint32_t row = q.row[p];
+    uint32_t st = 0;
+    if (row < q.nbuf) {  // wave-uniform
+        if (a.p.status[row] & SDFS_CDC_READ_CORRUPT) {
+            st = SDFS_CDC_READ_CORRUPT;
+        } else {
+            const uint64_t base = (uint64_t)row * a.p.cap;
+            const int64_t start = q.start[p], end = start + (int64_t)q.len[p];
+            const uint32_t hi = first_at_least(a.p.pos + base, used[row], end);  // pos < start + len below it
+            bool missing = false;
+            for (uint32_t i = lane; i < hi; i += 64) {
+                const int64_t nlen = a.p.nlen[base + i];
+                if (nlen == 0 || a.p.pos[base + i] + nlen <= start) continue;
+                const uint64_t hl = a.p.hashloc[base + i];
+                missing |= hl < a.pos_base || hl - a.pos_base >= a.n_store;
+            }
+            if (wave_any(missing)) {
+                st = SDFS_CDC_READ_MISSING;
+            } else {
+                for (uint32_t i = lane; i < hi; i += 64) {
+                    const int64_t nlen = a.p.nlen[base + i];
+                    if (nlen == 0 || a.p.pos[base + i] + nlen <= start) continue;
+                    const uint32_t f = (uint32_t)(a.p.hashloc[base + i] - a.pos_base);
+                    a.pair_fetch[base + i] = f;
+                    a.mark[f] = 1;
+                }
+            }
+        }
+    }
+    if (lane == 0) q.status[p] = st;
+}
+
+struct PieceWork {
+    uint8_t* bad;          // [nbuf*cap] 0, SDFS_CDC_READ_FETCH or SDFS_CDC_READ_BOUNDS per pair
+    uint32_t* win_lo;      // [n_pieces] the piece's window of pairs: first index in its row,
+    uint32_t* win_n;       // [n_pieces] and length
+    uint32_t* tiles;       // [n_pieces] 64 KiB tiles of the piece's output
+    uint32_t* tile_first;  // [n_pieces + 1] their exclusive prefix
+    uint32_t* any_big;     // [1] set when some piece's window exceeds kLdsPairs
+};
+
+// one wave per row: each pair's {end, running max of end, source offset}.  A pair that places
+// nothing — past the terminator, not needed, a failed fetch, out of bounds — gets end = pos, so it
+// covers no byte and does not raise the running max above any byte at or after its pos.
+__global__ __launch_bounds__(64) void pieces_rows_kernel(AsmArgs a, PieceWork w) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t base = (uint64_t)b * a.p.cap;
+    const uint32_t n = row_pairs(a.p, b);
+    const uint32_t used = row_used(a.p, base, n, lane);
+    int32_t carry = INT_MIN;
+    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        int32_t e = INT_MIN;
+        if (i < n) {
+            const int64_t pos = a.p.pos[base + i];
+            const uint32_t f = i < used ? a.pair_fetch[base + i] : kNone;
+            uint32_t bad = 0;
+            uint64_t src = 0;
+            e = (int32_t)pos;
+            if (f != kNone) {
+                const int64_t ck = a.fetch_len[f];
+                const int64_t nlen = a.p.nlen[base + i], off = a.p.offset[base + i];
+                const int64_t c = nlen > ck ? ck : nlen;
+                if (ck == (int64_t)UINT32_MAX) {
+                    bad = SDFS_CDC_READ_FETCH;
+                } else if (pos > (int64_t)a.chunk_length || pos + c > (int64_t)a.chunk_length || off + c > ck) {
+                    bad = SDFS_CDC_READ_BOUNDS;
+                } else {
+                    e = (int32_t)(pos + c);  // <= chunk_length <= INT32_MAX
+                    src = a.fetch_off[f] + (uint64_t)off;
+                }
+            }
+            a.end[base + i] = e;
+            a.src[base + i] = src;
+            w.bad[base + i] = (uint8_t)bad;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t v = __shfl_up(e, o);
+            if (lane >= (uint32_t)o) e = max(e, v);
+        }
+        e = max(e, carry);
+        if (i < n) a.maxend[base + i] = e;
+        carry = __shfl(e, 63);
+    }
+}
+
+// one wave per piece: FETCH / BOUNDS from its touching pairs, its window, its tile count
+__global__ __launch_bounds__(64) void pieces_status_kernel(AsmArgs a, PieceArgs q, PieceWork w) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t p = blockIdx.x;
+    const uint32_t row = q.row[p];
+    uint32_t st = q.status[p], lo = 0, cnt = 0;
+    if (row < q.nbuf && st == 0) {  // wave-uniform
+        const uint64_t base = (uint64_t)row * a.p.cap;
+        const int64_t start = q.start[p], end = start + (int64_t)q.len[p];
+        const uint32_t hi = first_at_least(a.p.pos + base, row_pairs(a.p, row), end);
+        bool failed = false, oob = false;
+        for (uint32_t i = lane; i < hi; i += 64) {
+            const int64_t nlen = a.p.nlen[base + i];
+            if (nlen == 0 || a.p.pos[base + i] + nlen <= start) continue;
+            failed |= w.bad[base + i] == SDFS_CDC_READ_FETCH;
+            oob |= w.bad[base + i] == SDFS_CDC_READ_BOUNDS;
+        }
+        if (wave_any(failed)) st = SDFS_CDC_READ_FETCH;
+        else if (wave_any(oob)) st = SDFS_CDC_READ_BOUNDS;
+        if (st == 0) {  // the window: maxend and pos are ascending
+            lo = first_at_least(a.maxend + base, hi, start + 1);
+            cnt = hi - lo;
+        }
+    }
+    if (lane == 0) {
+        const uint64_t head = reinterpret_cast<uintptr_t>(a.out + q.out_off[p]) & 15;
+        const uint64_t nvec = (head + q.len[p] + 15) / 16;
+        q.status[p] = st;
+        if (st && q.req_status && q.req[p] < q.n_requests) atomicOr(&q.req_status[q.req[p]], st);
+        if (cnt > kLdsPairs) *w.any_big = 1;
+        w.win_lo[p] = lo;
+        w.win_n[p] = cnt;
+        w.tiles[p] = q.len[p] ? (uint32_t)((nvec + kTileVecs - 1) / kTileVecs) : 0;
+    }
+}
+
+// The gather of the pieces: the tiles of all pieces in one list, walked with a grid stride.  A
+// tile finds its piece by a floor search in the prefix of the tile counts.  Two forms share the
+// list: LDS takes the tiles of the pieces whose window of pairs fits kLdsPairs and stages it (a
+// piece without a row or with a status has an empty window and is zero-filled here); the other
+// takes the tiles of the larger windows and searches them in global memory — it returns at once
+// when the status kernel saw no such piece.
+template <bool LDS>
+__global__ __launch_bounds__(kGatherThreads) void gather_pieces_kernel(AsmArgs a, PieceArgs q, PieceWork w) {
+    __shared__ int32_t s_pos[LDS ? kLdsPairs : 1], s_end[LDS ? kLdsPairs : 1], s_max[LDS ? kLdsPairs : 1];
+    __shared__ uint64_t s_src[LDS ? kLdsPairs : 1];
+    if (!LDS && *w.any_big == 0) return;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t total = w.tile_first[q.n_pieces];
+    for (uint32_t t = blockIdx.x; t < total; t += gridDim.x) {  // uniform over the workgroup
+        // the tile's piece is the same for every lane: keep what describes it in scalar registers
+        const uint32_t p = uni((uint32_t)floor_index<uint32_t>(w.tile_first, (int32_t)q.n_pieces, t, -2));
+        const int32_t n = (int32_t)uni(w.win_n[p]);
+        if ((n <= (int32_t)kLdsPairs) != LDS) continue;
+        const uint64_t v0 = (uint64_t)uni(t - w.tile_first[p]) * kTileVecs;
+        const uint64_t base = n ? (uint64_t)uni(q.row[p]) * a.p.cap + uni(w.win_lo[p]) : 0;
+        const uint64_t oo = q.out_off[p];
+        uint8_t* ob = a.out + ((uint64_t)uni((uint32_t)(oo >> 32)) << 32 | uni((uint32_t)oo));
+        const uint32_t start = uni(q.start[p]), len = uni(q.len[p]);
+        const uint32_t head = (uint32_t)(reinterpret_cast<uintptr_t>(ob) & 15);
+        PairView pv{a.p.pos + base, a.end + base, a.maxend + base, a.src + base, n};
+        if (LDS) {
+            __syncthreads();  // the tile before this one is done with the arrays
+            for (int32_t i = tid; i < n; i += kGatherThreads) {
+                s_pos[i] = pv.pos[i];
+                s_end[i] = pv.end[i];
+                s_max[i] = pv.maxend[i];
+                s_src[i] = pv.src[i];
+            }
+            __syncthreads();
+            pv.pos = s_pos;
+            pv.end = s_end;
+            pv.maxend = s_max;
+            pv.src = s_src;
+        }
+        gather_tile<false>(pv, a.chunks, ob, start, len, head, range_vecs(head, len), v0, tid);
     }
 }
 
@@ -600,6 +849,112 @@ int sdfs_cdc_read_assemble(int device, uint32_t nbuf, uint32_t chunk_length, con
     const dim3 grid((uint32_t)((uint64_t)tiles * nbuf));
     if (pairs->cap <= kLdsPairs) hipLaunchKernelGGL(gather_kernel<true>, grid, dim3(kGatherThreads), 0, s, a);
     else hipLaunchKernelGGL(gather_kernel<false>, grid, dim3(kGatherThreads), 0, s, a);
+    SDFS_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_split(const sdfs_cdc_read_file* files, uint32_t n_files, const sdfs_cdc_read_request* requests,
+                        uint32_t n_requests, uint32_t chunk_length, int64_t* n_read, uint32_t piece_cap,
+                        uint32_t* piece_req, uint32_t* piece_row, uint32_t* piece_start, uint32_t* piece_len,
+                        uint64_t* piece_out_off, uint32_t row_cap, uint64_t* row_slot, uint64_t* n_pieces,
+                        uint64_t* n_rows) {
+    const char* why = "";
+    const int rc = read_split(files, n_files, requests, n_requests, chunk_length, n_read, piece_cap, piece_req, piece_row,
+                              piece_start, piece_len, piece_out_off, row_cap, row_slot, n_pieces, n_rows, &why);
+    if (rc == SDFS_CDC_ECAP)
+        return fail_status(rc, "%llu pieces of %llu rows: piece_cap %u, row_cap %u", (unsigned long long)*n_pieces,
+                           (unsigned long long)*n_rows, piece_cap, row_cap);
+    return rc ? fail_status(rc, "%s", why) : SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_plan_pieces(int device, uint32_t nbuf, const sdfs_cdc_pairs* pairs, uint64_t pos_base,
+                              uint64_t n_store, const uint64_t* d_store_off, const uint32_t* d_store_len,
+                              const uint32_t* d_store_raw_len, uint32_t n_pieces, const uint32_t* d_piece_row,
+                              const uint32_t* d_piece_start, const uint32_t* d_piece_len, uint32_t* d_piece_status,
+                              uint32_t* d_pair_fetch, uint32_t* d_fetch_count, uint64_t* d_src_off, uint32_t* d_src_len,
+                              uint64_t* d_dst_off, uint32_t* d_dst_cap, uint64_t* d_plain_off, uint64_t* d_total_bytes,
+                              void* stream) {
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (!d_fetch_count || !d_total_bytes || (nbuf && !d_pair_fetch)) return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_store && (!d_store_off || !d_store_len || !d_store_raw_len || !d_src_off || !d_src_len || !d_dst_off ||
+                    !d_dst_cap))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_pieces && (!d_piece_row || !d_piece_start || !d_piece_len || !d_piece_status))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_store >= UINT32_MAX) return fail_status(SDFS_CDC_EINVAL, "n_store %llu: fetch indices are 32-bit",
+                                                  (unsigned long long)n_store);
+    if (n_pieces > (uint32_t)INT32_MAX) return fail_status(SDFS_CDC_EINVAL, "%u pieces: split the batch", n_pieces);
+    if (const int rc = set_device(device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Scratch sc(s);
+    PlanArgs a{*pairs,    pos_base,  n_store,   d_store_off, d_store_len, d_store_raw_len, d_pair_fetch, d_fetch_count,
+               d_src_off, d_src_len, d_dst_off, d_dst_cap,   d_plain_off, d_total_bytes,   nullptr};
+    const PieceArgs q{nbuf, n_pieces, d_piece_row, d_piece_start, d_piece_len, nullptr, d_piece_status, nullptr, 0, nullptr};
+    uint32_t* used = nullptr;
+    SDFS_TRY(sc.get(&a.mark, (size_t)n_store));
+    SDFS_TRY(sc.get(&used, nbuf));
+    SDFS_TRY(hipMemsetAsync(a.mark, 0, std::max<size_t>(n_store, 1) * 4, s));
+    if (nbuf) hipLaunchKernelGGL(plan_rows_kernel, dim3(nbuf), dim3(64), 0, s, a, used);
+    if (n_pieces) hipLaunchKernelGGL(plan_mark_pieces_kernel, dim3(n_pieces), dim3(64), 0, s, a, q, used);
+    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+    const uint64_t slots = (uint64_t)nbuf * pairs->cap;
+    if (slots)
+        hipLaunchKernelGGL(plan_remap_kernel, dim3((uint32_t)((slots + 255) / 256)), dim3(256), 0, s, d_pair_fetch, slots,
+                           a.mark);
+    SDFS_TRY(hipGetLastError());
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_read_assemble_pieces(int device, uint32_t nbuf, uint32_t chunk_length, const sdfs_cdc_pairs* pairs,
+                                  const uint32_t* d_pair_fetch, const uint8_t* d_chunks, const uint64_t* d_fetch_off,
+                                  const uint32_t* d_fetch_len, uint32_t n_pieces, const uint32_t* d_piece_row,
+                                  const uint32_t* d_piece_start, const uint32_t* d_piece_len,
+                                  const uint64_t* d_piece_out_off, uint32_t* d_piece_status,
+                                  const uint32_t* d_piece_req, uint32_t n_requests, uint32_t* d_req_status,
+                                  uint8_t* d_out, void* stream) {
+    if (!pairs_complete(pairs)) return fail_status(SDFS_CDC_EINVAL, "incomplete sdfs_cdc_pairs");
+    if (const int rc = check_chunk_length(chunk_length)) return rc;
+    if (nbuf && (!d_pair_fetch || !d_chunks || !d_fetch_off || !d_fetch_len))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (n_pieces && (!d_piece_row || !d_piece_start || !d_piece_len || !d_piece_out_off || !d_piece_status || !d_out))
+        return fail_status(SDFS_CDC_EINVAL, "null argument");
+    if (d_req_status && n_requests && n_pieces && !d_piece_req)
+        return fail_status(SDFS_CDC_EINVAL, "d_req_status without d_piece_req");
+    const uint32_t tiles = (uint32_t)(((uint64_t)chunk_length + 30) / 16 / kTileVecs + 1);  // of one piece, at most
+    if ((uint64_t)tiles * n_pieces > (uint64_t)INT32_MAX)
+        return fail_status(SDFS_CDC_EINVAL, "%u pieces of up to %u bytes: split the batch", n_pieces, chunk_length);
+    if (n_pieces == 0 && !(d_req_status && n_requests)) return SDFS_CDC_OK;
+    if (const int rc = set_device(device)) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (d_req_status && n_requests) SDFS_TRY(hipMemsetAsync(d_req_status, 0, (size_t)n_requests * 4, s));
+    if (n_pieces == 0) return SDFS_CDC_OK;
+    Scratch sc(s);
+    AsmArgs a{*pairs, nbuf, chunk_length, d_pair_fetch, d_chunks, d_fetch_off, d_fetch_len, d_out,
+              nullptr, nullptr, nullptr, nullptr, 0};
+    const PieceArgs q{nbuf,           n_pieces,    d_piece_row, d_piece_start, d_piece_len, d_piece_out_off,
+                      d_piece_status, d_piece_req, n_requests,  n_requests ? d_req_status : nullptr};
+    PieceWork w{};
+    const size_t slots = (size_t)nbuf * pairs->cap;
+    uint32_t* per_piece = nullptr;  // win_lo, win_n, tiles, tile_first, any_big
+    SDFS_TRY(sc.get(&a.end, slots));
+    SDFS_TRY(sc.get(&a.maxend, slots));
+    SDFS_TRY(sc.get(&a.src, slots));
+    SDFS_TRY(sc.get(&w.bad, slots));
+    SDFS_TRY(sc.get(&per_piece, (size_t)n_pieces * 4 + 2));
+    w.win_lo = per_piece;
+    w.win_n = per_piece + n_pieces;
+    w.tiles = per_piece + (size_t)n_pieces * 2;
+    w.tile_first = per_piece + (size_t)n_pieces * 3;
+    w.any_big = per_piece + (size_t)n_pieces * 4 + 1;
+    SDFS_TRY(hipMemsetAsync(w.any_big, 0, 4, s));
+    if (nbuf) hipLaunchKernelGGL(pieces_rows_kernel, dim3(nbuf), dim3(64), 0, s, a, w);
+    hipLaunchKernelGGL(pieces_status_kernel, dim3(n_pieces), dim3(64), 0, s, a, q, w);
+    hipLaunchKernelGGL(prefix_kernel<uint32_t>, dim3(1), dim3(1024), 0, s, w.tiles, n_pieces, w.tile_first);
+    const uint64_t bound = (uint64_t)tiles * n_pieces;  // of the tile count, known without a host read
+    hipLaunchKernelGGL(gather_pieces_kernel<true>, dim3((uint32_t)std::min<uint64_t>(bound, kPieceGrid)),
+                       dim3(kGatherThreads), 0, s, a, q, w);
+    hipLaunchKernelGGL(gather_pieces_kernel<false>, dim3((uint32_t)std::min<uint64_t>(bound, kPieceGridBig)),
+                       dim3(kGatherThreads), 0, s, a, q, w);
     SDFS_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }

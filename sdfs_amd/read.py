@@ -9,7 +9,10 @@ into a zeroed CHUNK_LENGTH array.
 
 * :func:`parse_map_slots` — the slots' images as a :class:`ParsedPairs` (device tensors).
 * :class:`HipBufferReader` — the whole path for a batch of buffers: parse -> plan -> (decrypt ->
-  chain_lens) -> framed decode -> assemble -> (verify).
+  chain_lens) -> framed decode -> assemble -> (verify); ``read_ranges`` / ``read_file`` —
+  ``DedupFileChannel.read`` (DedupFileChannel.java:499-608) for batches of byte ranges: split ->
+  parse of the touched slots -> plan_pieces -> the same middle -> assemble_pieces -> (verify).
+* :func:`split_requests`, :func:`plan_pieces`, :func:`assemble_pieces` — the ranged read's steps.
 
 PyTorch allocates HBM and hands over the stream; every step runs the library's HIP kernels.
 No CPU fallback: a failure raises :class:`SdfsCdcError`.
@@ -135,6 +138,127 @@ def verify_reads(engine, pairs: ParsedPairs, pair_fetch, chunks, fetch_off, fetc
 
 
 @dataclass
+class Pieces:
+    """``sdfs_cdc_read_split``'s outputs (host numpy arrays): request r read n_read[r] bytes (-1 =
+    at or past the end of the file); piece p is [start[p], start[p] + len[p]) of row row[p] (-1: past
+    the map, zeros) and goes to out_off[p]; rows = the distinct touched slots, ascending."""
+
+    n_read: object   # int64 [n_requests]
+    req: object      # int32 [n_pieces]
+    row: object      # int32 [n_pieces], -1 = no row
+    start: object    # int32 [n_pieces]
+    len: object      # int32 [n_pieces]
+    out_off: object  # int64 [n_pieces]
+    rows: object     # int64 [n_rows] slot indices
+
+
+def _u64_table(rows, width: int, what: str):
+    import numpy as np
+
+    a = np.asarray(rows)
+    if a.size == 0:
+        return np.zeros((0, width), np.uint64)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{what}: {width} integers each")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: integers")
+    if a.dtype.kind == "i" and (a < 0).any():
+        raise ValueError(f"{what}: a negative value")
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def split_requests(files, requests, chunk_length: int) -> Pieces:
+    """``sdfs_cdc_read_split`` (host): ``DedupFileChannel.read``'s request layer.  files: rows of
+    (first_slot, n_slots, file_len); requests: rows of (file, file_pos, siz, out_off)."""
+    import numpy as np
+
+    lib = _lib.load()
+    f = _u64_table(files, 3, "files")
+    q = _u64_table(requests, 4, "requests")
+    n_read = np.zeros(max(len(q), 1), np.int64)
+    np_, nr = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    ip = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    # the documented bound, clipped: a first call that runs short reports the counts
+    per = np.minimum(q[:, 2] // np.uint64(max(int(chunk_length), 1)), np.uint64(1 << 20)) + np.uint64(2)
+    cap = min(int(per.sum()), 1 << 20)
+    while True:
+        u32 = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+        out_off = np.zeros(max(cap, 1), np.uint64)
+        rows = np.zeros(max(cap, 1), np.uint64)
+        rc = lib.sdfs_cdc_read_split(ip(f), len(f), ip(q), len(q), int(chunk_length), ip(n_read), cap, ip(u32[0]),
+                                     ip(u32[1]), ip(u32[2]), ip(u32[3]), ip(out_off), cap, ip(rows),
+                                     ctypes.byref(np_), ctypes.byref(nr))
+        if rc != _lib.ECAP:
+            break
+        cap = int(np_.value)  # rows <= pieces
+    check(rc)
+    n, r = int(np_.value), int(nr.value)
+    return Pieces(n_read[:len(q)], u32[0][:n].view(np.int32), u32[1][:n].view(np.int32), u32[2][:n].view(np.int32),
+                  u32[3][:n].view(np.int32), out_off[:n].view(np.int64), rows[:r].view(np.int64))
+
+
+def plan_pieces(pairs: ParsedPairs, piece_row, piece_start, piece_len, store_off, store_len, store_raw_len,
+                pos_base: int, device: int = 0, stream=None):
+    """``sdfs_cdc_read_plan_pieces``.  piece_row / piece_start / piece_len: device int32 [n_pieces]
+    (row -1 = no row).  Returns :func:`plan_reads`' dict plus piece_status int32 [n_pieces]."""
+    import torch
+
+    n = int(store_len.shape[0])
+    npc = int(piece_row.shape[0])
+    dev = pairs.counts.device
+    e = lambda dt: torch.empty(max(n, 1), dtype=dt, device=dev)  # noqa: E731
+    out = dict(pair_fetch=torch.empty((max(pairs.nbuf, 1), pairs.cap), dtype=torch.int32, device=dev),
+               fetch_count=torch.zeros(1, dtype=torch.int32, device=dev), src_off=e(torch.int64),
+               src_len=e(torch.int32), dst_off=e(torch.int64), dst_cap=e(torch.int32), plain_off=e(torch.int64),
+               total_bytes=torch.zeros(2, dtype=torch.int64, device=dev),
+               piece_status=torch.zeros(max(npc, 1), dtype=torch.int32, device=dev)[:npc])
+    check(_lib.load().sdfs_cdc_read_plan_pieces(
+        int(device), pairs.nbuf, ctypes.byref(pairs.c), int(pos_base), n, store_off.data_ptr() if n else None,
+        store_len.data_ptr() if n else None, store_raw_len.data_ptr() if n else None, npc,
+        piece_row.data_ptr() if npc else None, piece_start.data_ptr() if npc else None,
+        piece_len.data_ptr() if npc else None, out["piece_status"].data_ptr() if npc else None,
+        out["pair_fetch"].data_ptr(), out["fetch_count"].data_ptr(), out["src_off"].data_ptr(),
+        out["src_len"].data_ptr(), out["dst_off"].data_ptr(), out["dst_cap"].data_ptr(), out["plain_off"].data_ptr(),
+        out["total_bytes"].data_ptr(), stream_of(pairs.counts, stream)))
+    return out
+
+
+def assemble_pieces(pairs: ParsedPairs, chunk_length: int, pair_fetch, chunks, fetch_off, fetch_len, piece_row,
+                    piece_start, piece_len, piece_out_off, piece_status, out, piece_req=None, n_requests: int = 0,
+                    device: int = 0, stream=None):
+    """``sdfs_cdc_read_assemble_pieces``: settles piece_status (in/out) and writes piece p to
+    out[piece_out_off[p] : + piece_len[p]] (``out``: device uint8, flat).  With piece_req (device
+    int32 [n_pieces]) and n_requests it returns the per-request status, int32 [n_requests]."""
+    import torch
+
+    npc = int(piece_row.shape[0])
+    req_status = None
+    if piece_req is not None:
+        req_status = torch.empty(max(n_requests, 1), dtype=torch.int32, device=chunks.device)[:n_requests]
+    if npc or n_requests:
+        p = lambda t: t.data_ptr() if npc else None  # noqa: E731
+        check(_lib.load().sdfs_cdc_read_assemble_pieces(
+            int(device), pairs.nbuf, int(chunk_length), ctypes.byref(pairs.c), pair_fetch.data_ptr(),
+            chunks.data_ptr(), fetch_off.data_ptr(), fetch_len.data_ptr(), npc, p(piece_row), p(piece_start),
+            p(piece_len), p(piece_out_off), p(piece_status), p(piece_req) if piece_req is not None else None,
+            int(n_requests) if piece_req is not None else 0, ptr(req_status) if n_requests else None,
+            out.data_ptr() if npc else None, stream_of(chunks, stream)))
+    return out if req_status is None else req_status
+
+
+@dataclass
+class RangeInfo:
+    fetch_count: int        # distinct stored records the batch needed
+    pieces: Pieces
+    piece_status: object    # int32 [n_pieces], SDFS_CDC_READ_* bits
+    rows: object            # int64 [n_rows] (device): the parsed slots, ``pairs`` row i = slot rows[i]
+    pairs: ParsedPairs
+    pair_fetch: object      # int32 [n_rows, cap], -1 = not needed
+    bad_count: object = None  # verify: int32 [n_rows]
+    pair_bad: object = None   # verify: uint8 [n_rows, cap]
+
+
+@dataclass
 class ReadInfo:
     fetch_count: int        # distinct stored records the batch needed
     pairs: ParsedPairs
@@ -178,24 +302,13 @@ class HipBufferReader:
             self.aes.destroy()
             self.aes = None
 
-    def read(self, map_slots, nbuf: int, slot_len: int, store, store_off, store_len, store_raw_len, pos_base: int,
-             verify: bool = False, out=None, stages=None, store_ivs=None):
-        """map_slots: device uint8, nbuf slots of slot_len bytes.  store: device uint8 holding the
-        putChunk records ``[BE32 nz][payload]`` (AES-CBC ciphertext of them when ``aes`` is set);
-        record of hashloc pos_base + k at store[store_off[k] : + store_len[k]], its chunk
-        store_raw_len[k] bytes long.  Returns (buffers uint8 [nbuf, chunk_length], status int32
-        [nbuf], :class:`ReadInfo`).  ``out``: optional uint8 [nbuf, chunk_length] to write into.  ``stages``: optional callable(name) called after each stage is
-        enqueued (measurements).  ``store_ivs``: optional device uint8 [n_store, 16], the IV of each
-        directory entry's record, for a store whose archives have IVs of their own
-        (``ArchiveSet.record_ivs()``); default: ``iv`` for every record."""
+    def _fetch(self, pairs, plan, store, pos_base, store_ivs, mark):
+        """The middle of every read: the planned records decrypted (an encrypted store), then decoded
+        into one chunk area.  Returns (fetch count, chunks, fetch_off, fetch_len) as the assemble and
+        verify entry points take them."""
         import torch
 
-        mark = stages or (lambda name: None)
         dev = store.device
-        pairs = parse_map_slots(map_slots, nbuf, slot_len, self.hash_len, self.device)
-        mark("parse")
-        plan = plan_reads(pairs, store_off, store_len, store_raw_len, pos_base, self.device)
-        mark("plan")
         # the one host read: the scratch sizes
         chunk_bytes, plain_bytes = (int(v) for v in plan["total_bytes"].tolist())
         k = int(plan["fetch_count"].item())
@@ -227,6 +340,27 @@ class HipBufferReader:
         if k == 0:  # assemble still needs valid pointers
             dst_off = plan["dst_off"]
             fetch_len = torch.zeros(1, dtype=torch.int32, device=dev)
+        return k, chunks, dst_off, fetch_len
+
+    def read(self, map_slots, nbuf: int, slot_len: int, store, store_off, store_len, store_raw_len, pos_base: int,
+             verify: bool = False, out=None, stages=None, store_ivs=None):
+        """map_slots: device uint8, nbuf slots of slot_len bytes.  store: device uint8 holding the
+        putChunk records ``[BE32 nz][payload]`` (AES-CBC ciphertext of them when ``aes`` is set);
+        record of hashloc pos_base + k at store[store_off[k] : + store_len[k]], its chunk
+        store_raw_len[k] bytes long.  Returns (buffers uint8 [nbuf, chunk_length], status int32
+        [nbuf], :class:`ReadInfo`).  ``out``: optional uint8 [nbuf, chunk_length] to write into.  ``stages``: optional callable(name) called after each stage is
+        enqueued (measurements).  ``store_ivs``: optional device uint8 [n_store, 16], the IV of each
+        directory entry's record, for a store whose archives have IVs of their own
+        (``ArchiveSet.record_ivs()``); default: ``iv`` for every record."""
+        import torch
+
+        mark = stages or (lambda name: None)
+        dev = store.device
+        pairs = parse_map_slots(map_slots, nbuf, slot_len, self.hash_len, self.device)
+        mark("parse")
+        plan = plan_reads(pairs, store_off, store_len, store_raw_len, pos_base, self.device)
+        mark("plan")
+        k, chunks, dst_off, fetch_len = self._fetch(pairs, plan, store, pos_base, store_ivs, mark)
         out = assemble(pairs, self.chunk_length, plan["pair_fetch"], chunks, dst_off, fetch_len, out=out,
                        device=self.device)
         mark("assemble")
@@ -242,3 +376,82 @@ class HipBufferReader:
                 info.bad_count = torch.zeros(nbuf, dtype=torch.int32, device=dev)
             mark("verify")
         return out, pairs.status[:nbuf], info
+
+    def read_ranges(self, map_slots, nslots: int, slot_len: int, files, requests, store, store_off, store_len,
+                    store_raw_len, pos_base: int, verify: bool = False, out=None, stages=None, store_ivs=None):
+        """``DedupFileChannel.read`` (DedupFileChannel.java:499-608) for a batch of byte ranges.
+        map_slots: device uint8, one map image of nslots slots of slot_len bytes; files: rows of
+        (first_slot, n_slots, file_len) over that image; requests: rows of (file, file_pos, siz,
+        out_off).  Only the touched slots are parsed and only the records of the pairs that touch a
+        range are fetched; the store arguments are :meth:`read`'s.  Returns (out uint8, flat: request
+        r's bytes at out[out_off : out_off + n_read[r]]; n_read int64 numpy [n_requests], -1 = at or
+        past the end of the file; status int32 [n_requests] (device), the OR of the request's pieces;
+        :class:`RangeInfo`).  ``out``: optional device uint8 to write into — no byte outside the
+        requests' extents is touched.  A bad record fails only the ranges that touch it, where
+        :meth:`read` fails the whole buffer."""
+        import numpy as np
+        import torch
+
+        mark = stages or (lambda name: None)
+        dev = store.device
+        pc = split_requests(files, requests, self.chunk_length)
+        n_req, npc, nrows = len(pc.n_read), len(pc.req), len(pc.rows)
+        if nrows and int(pc.rows[-1]) >= int(nslots):
+            raise ValueError(f"a file names slot {int(pc.rows[-1])}, the image holds {nslots}")
+        if map_slots.numel() < int(nslots) * int(slot_len):
+            raise ValueError(f"map holds {map_slots.numel()} bytes, {nslots} slots of {slot_len} need more")
+        need = int((pc.out_off + pc.len).max()) if npc else 0
+        if out is None:
+            out = torch.zeros(max(need, 1), dtype=torch.uint8, device=dev)[:need]
+        elif out.numel() < need or not out.is_contiguous():
+            raise ValueError(f"out holds {out.numel()} bytes, the requests end at {need}")
+        # one upload: the pieces' int32 columns, then their out_off and the rows as int64
+        n4 = (4 * npc + 1) // 2
+        host = np.zeros(n4 + npc + nrows + 1, np.int64)
+        host[:n4].view(np.int32)[:4 * npc] = np.concatenate([pc.req, pc.row, pc.start, pc.len])
+        host[n4:n4 + npc] = pc.out_off
+        host[n4 + npc:n4 + npc + nrows] = pc.rows
+        d = torch.from_numpy(host).to(dev)
+        d32 = d[:n4].view(torch.int32)
+        p_req, p_row, p_start, p_len = (d32[i * npc:(i + 1) * npc] for i in range(4))
+        p_out, rows = d[n4:n4 + npc], d[n4 + npc:n4 + npc + nrows]
+        mark("split")
+        images = map_slots[:int(nslots) * int(slot_len)].view(int(nslots), int(slot_len))[rows].contiguous()
+        pairs = parse_map_slots(images, nrows, slot_len, self.hash_len, self.device)
+        mark("parse")
+        plan = plan_pieces(pairs, p_row, p_start, p_len, store_off, store_len, store_raw_len, pos_base, self.device)
+        mark("plan")
+        k, chunks, dst_off, fetch_len = self._fetch(pairs, plan, store, pos_base, store_ivs, mark)
+        status = plan["piece_status"]
+        req_status = assemble_pieces(pairs, self.chunk_length, plan["pair_fetch"], chunks, dst_off, fetch_len, p_row,
+                                     p_start, p_len, p_out, status, out, piece_req=p_req, n_requests=n_req,
+                                     device=self.device)
+        mark("assemble")
+        info = RangeInfo(k, pc, status, rows, pairs, plan["pair_fetch"])
+        if verify:
+            if self.engine is None:
+                raise ValueError("verify=True needs the hash engine")
+            if k and nrows:
+                info.pair_bad, info.bad_count = verify_reads(self.engine, pairs, plan["pair_fetch"], chunks, dst_off,
+                                                             fetch_len, plan["fetch_count"])
+            else:
+                info.pair_bad = torch.zeros((nrows, pairs.cap), dtype=torch.uint8, device=dev)
+                info.bad_count = torch.zeros(nrows, dtype=torch.int32, device=dev)
+            mark("verify")
+        return out, pc.n_read, req_status, info
+
+    def read_file(self, map_slots, nslots: int, slot_len: int, file_len: int, file_pos: int, siz: int, store,
+                  store_off, store_len, store_raw_len, pos_base: int, verify: bool = False, store_ivs=None):
+        """One ``DedupFileChannel.read(buf, 0, siz, file_pos)`` on a file that owns the whole image:
+        the bytes read, ``None`` at or past the end of the file (the reference's -1).  Raises
+        :class:`SdfsCdcError` when the range's status is not 0, as the Java call throws."""
+        out, n_read, status, info = self.read_ranges(map_slots, nslots, slot_len, [(0, nslots, file_len)],
+                                                     [(0, file_pos, siz, 0)], store, store_off, store_len,
+                                                     store_raw_len, pos_base, verify=verify, store_ivs=store_ivs)
+        if int(n_read[0]) < 0:
+            return None
+        st = int(status[0].item())
+        if st:
+            raise _lib.SdfsCdcError(st, f"read of [{file_pos}, {file_pos + int(n_read[0])}) failed: "
+                                        f"status {st:#x} (SDFS_CDC_READ_* bits)")
+        return out[:int(n_read[0])].cpu().numpy().tobytes()
