@@ -170,6 +170,34 @@ int sdfs_cdc_index_claim_slots(sdfs_cdc_index* ix, uint8_t* d_map, uint64_t nslo
                                uint32_t* d_slot_status, uint32_t* d_slot_missed, uint64_t* d_counts,
                                void* stream);
 
+/* writeSparseDataChunk for a batch of requests (StorageServiceImpl.java:275-382): the pairs of a
+ * request whose `inserted` flag is not set are grouped by hash, DedupFileStore.addRef(hash, hashloc,
+ * ct) must answer the same position for every group, or the request fails with its misses
+ * (HashWriteException) and the slot is not written.  claim_slots applies whatever matches and
+ * counts the rest; here a request goes in whole or not at all.
+ *
+ * d_req: nreq images (nreq x slot_bytes), read by exactly the rule stated above: corrupt images,
+ * negative fields, the TreeMap rule for a repeated pos.  d_inserted (may be NULL = none):
+ * d_inserted[r * pair_stride + i] != 0 = pair i of request r is `inserted` (the client has just
+ * sent that chunk through writeChunks, whose put took the reference): a counting pair that is
+ * inserted is skipped entirely, neither probed nor counted; pair_stride >= the pairs a slot holds.
+ * A request is accepted iff it parses and EVERY counting pair that is not inserted names a
+ * fingerprint held at pos == hashloc; an accepted request adds 1 per such pair (d_status[r] = 0).
+ * A rejected one gets SDFS_CDC_INGEST_EMISSED (sdfs_ingest.h) or SDFS_CDC_READ_CORRUPT and moves NO
+ * count, whatever its other pairs match; it does not stand in the way of the other requests.
+ * d_req_missed[r] (required) = its misses; the first miss_cap misses are listed in d_miss_list as
+ * {u32 request, u32 pair}, in unspecified order (may be NULL when miss_cap = 0).  d_counts
+ * (required, device u64[6]) = {pairs added, pairs missed, pairs skipped as inserted, requests
+ * accepted, requests rejected, misses listed}.
+ * Validation, a check pass that probes and counts the misses, and an apply pass that runs only
+ * where there were none are kernels of their own, so the decision holds across the several waves
+ * that share a slot of thousands of pairs, and the result does not depend on the schedule.
+ * The hashloc 0 / 1 and blank-hash skips of addRef are not mirrored (see above). */
+int sdfs_cdc_index_addref_slots(sdfs_cdc_index* ix, const uint8_t* d_req, uint64_t nreq, uint32_t slot_bytes,
+                                uint32_t hash_len, const uint8_t* d_inserted, uint32_t pair_stride,
+                                uint32_t* d_status, uint32_t* d_req_missed, uint32_t* d_miss_list,
+                                uint64_t miss_cap, uint64_t* d_counts, void* stream);
+
 /* The audit: do the counts still match the files?  The same walk, but every counting pair whose
  * digest is held at pos == hashloc adds 1 to a shadow count of that fingerprint (zeroed by this
  * call; any other pair is missed); then every held entry's count (have) is compared with its

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
                                for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h",
-                                         "sdfs_extent.h", "sdfs_lz4_stream.h")]
+                                         "sdfs_extent.h", "sdfs_lz4_stream.h", "sdfs_ingest.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -207,6 +207,27 @@ class Inserts(ctypes.Structure):
 # SDFS_CDC_EXT_*
 EXT_CORRUPT, EXT_OVERLAP, EXT_BAD_INSERT, EXT_OVERFLOW, EXT_ECAP, EXT_HOLE, EXT_SRC = 1, 2, 4, 8, 16, 32, 64
 
+class IngestBatch(ctypes.Structure):
+    """``sdfs_cdc_ingest_batch`` (include/sdfs_ingest.h): the client's entries, device pointers."""
+
+    _fields_ = [("hash", ctypes.c_void_p), ("blob", ctypes.c_void_p), ("blob_bytes", ctypes.c_uint64),
+                ("off", ctypes.c_void_p), ("len", ctypes.c_void_p), ("raw_len", ctypes.c_void_p),
+                ("compressed", ctypes.c_void_p), ("n", ctypes.c_uint64)]
+
+
+class IngestPlan(ctypes.Structure):
+    """``sdfs_cdc_ingest_plan``: what the plan lays out, device pointers."""
+
+    _fields_ = [("status", ctypes.c_void_p), ("stage_off", ctypes.c_void_p), ("rec_of", ctypes.c_void_p),
+                ("dec_src_off", ctypes.c_void_p), ("dec_src_len", ctypes.c_void_p), ("dec_dst_off", ctypes.c_void_p),
+                ("dec_cap", ctypes.c_void_p), ("dec_len", ctypes.c_void_p), ("dec_entry", ctypes.c_void_p),
+                ("dec_count", ctypes.c_void_p), ("staged", ctypes.c_void_p)]
+
+
+# SDFS_CDC_INGEST_*
+INGEST_EMPTY, INGEST_EBOUNDS, INGEST_EDECODE, INGEST_EHASH, INGEST_EMISSED = 1, 2, 4, 8, 16
+INGEST_NONE, INGEST_TILE, INGEST_COPY_SPAN = 0xFFFFFFFF, 1024, 65536
+
 # (name, restype, argtypes) for every entry point of include/sdfs_cdc.h
 _P = ctypes.POINTER
 _u8p, _u32p, _u64p, _vp = _P(ctypes.c_uint8), _P(ctypes.c_uint32), _P(ctypes.c_uint64), ctypes.c_void_p
@@ -271,6 +292,8 @@ SIGNATURES = {
                                                   ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp, _vp]),
     "sdfs_cdc_index_recount": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp,
                                               ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_index_addref_slots": (ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp,
+                                                   ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "sdfs_cdc_index_load": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "sdfs_cdc_index_export": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     # include/sdfs_lz4.h
@@ -376,6 +399,16 @@ SIGNATURES = {
     "sdfs_cdc_lz4_stream_scan_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     "sdfs_cdc_lz4_stream_decompress_device": (ctypes.c_int, [_vp, _vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_uint64,
                                                              _vp, _vp, _vp, _vp]),
+    # include/sdfs_ingest.h
+    "sdfs_cdc_ingest_chunks_plan": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), ctypes.c_uint32, ctypes.c_uint64,
+                                                   _P(IngestPlan), _vp]),
+    "sdfs_cdc_ingest_chunks_decode": (ctypes.c_int, [_vp, _P(IngestBatch), _P(IngestPlan), _vp, _vp]),
+    "sdfs_cdc_ingest_chunks_copy": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), _P(IngestPlan), ctypes.c_uint32, _vp,
+                                                   _vp]),
+    "sdfs_cdc_ingest_chunks_verify": (ctypes.c_int, [_vp, _P(IngestBatch), _P(IngestPlan), _vp, ctypes.c_uint32, _vp]),
+    "sdfs_cdc_ingest_chunks_records": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), _P(IngestPlan), _vp, _vp, _vp]),
+    "sdfs_cdc_ingest_chunks_results": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), _P(IngestPlan), _vp, _vp,
+                                                      ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -371,32 +371,47 @@ class HipBufferWriter:
     def write(self, batch, pos_base: int, ivs=None, buffer_id_base: int = 0, run: bool = True):
         """-> (map_slots uint8 [nbuf * slot_len], :class:`ArchiveSet`).  ivs: uint8 [>= n_arc, 16] device
         tensor, the archives' IVs in order (default: random)."""
-        import torch
-
         from .meta import emit_map_slots
 
-        A = self.archiver
         if run:
             batch.run(buffer_id_base=buffer_id_base)
-        dev = batch.data.device
         recs = batch.recs.view(-1, _lib.RECORD_BYTES)
-        n = int(recs.shape[0])
         dup, loc, new, nc = self.index.put_records(recs, batch.total, pos_base=pos_base)
+        arcs = self.store_new(batch.data, batch.nbytes, recs, new, nc, ivs=ivs, buffer_id_base=buffer_id_base,
+                              uniform_len=batch.buf_len)
+        m, doop, ovf = emit_map_slots(batch, dup, loc, hash_len=self.hash_len, device=self.device)
+        arcs.extra.update(dup=dup, hashloc=loc, doop=doop, overflow=ovf, new_list=new[: arcs.n_rec])
+        return m, arcs
+
+    def store_new(self, src, nbytes: int, recs, new, nc, ivs=None, buffer_id_base: int = 0, uniform_len: int = 0,
+                  buf_offs=None) -> ArchiveSet:
+        """What happens to the records ``put_records`` inserted: LZ4 framing or the raw frame, AES,
+        archive plan, pack, ``.map`` images.  src: the bytes the records' chunks lie in (``nbytes`` of
+        them at most are chunk data); recs: the 48-byte fingerprint records; new / nc: put_records'
+        ``new_list`` and ``new_count``; where a record's buffer starts in src: ``buf_offs`` (device
+        int64, by buffer_id - buffer_id_base) or ``uniform_len`` times that.  Shared by :meth:`write`
+        and :meth:`sdfs_amd.ingest.HipChunkIngest.write_chunks`."""
+        import torch
+
+        A = self.archiver
+        dev = src.device
+        n = int(recs.shape[0])
+        nbytes = int(nbytes)
         cnt = nc.view(torch.int32)[:1]
         src_off, src_len, dst_off, _ = self._z.plan_records(recs, sel=new, count=cnt, buffer_id_base=buffer_id_base,
-                                                            uniform_len=batch.buf_len, framed=True)
+                                                            uniform_len=uniform_len, buf_offs=buf_offs, framed=True)
         live = torch.arange(n, device=dev) < nc  # the entries past the count are not written by anyone
         src_len = torch.where(live, src_len, torch.zeros_like(src_len))
         # worst case of all: every byte of the batch new, every slot a chunk (no host read)
-        room = _r16(batch.nbytes + batch.nbytes // 255 + 36 * n) + 16
+        room = _r16(nbytes + nbytes // 255 + 36 * n) + 16
         # archives: each but the last reaches blocksz or the entry limit
         arc_cap = room // min(A.blocksz) + n // max(A.limit, 1) + 2
-        data, rec_off, rec_len, raw = batch.data, src_off, src_len, False
+        data, rec_off, rec_len, raw = src, src_off, src_len, False
         if self.compress:
             data = torch.empty(room, dtype=torch.uint8, device=dev)
             rec_len = torch.zeros(n, dtype=torch.int32, device=dev)
             rec_off = dst_off
-            self._z.compress_device(batch.data, src_off, src_len, data, dst_off, rec_len, count=cnt, framed=True)
+            self._z.compress_device(src, src_off, src_len, data, dst_off, rec_len, count=cnt, framed=True)
         elif self.aes is None:
             raw = True
         prepare = None
@@ -418,11 +433,8 @@ class HipBufferWriter:
                                         nz_prefix=None if self.compress else -1)
 
             data, rec_off, rec_len = enc, enc_off, enc_len
-        arcs = A.archive(data, rec_off, rec_len, recs, sel=new, count=cnt, rec_len=plan_len, raw_len=src_len,
+        return A.archive(data, rec_off, rec_len, recs, sel=new, count=cnt, rec_len=plan_len, raw_len=src_len,
                          ivs=ivs, arc_cap=arc_cap, raw_frame=raw, prepare=prepare)
-        m, doop, ovf = emit_map_slots(batch, dup, loc, hash_len=self.hash_len, device=self.device)
-        arcs.extra.update(dup=dup, hashloc=loc, doop=doop, overflow=ovf, new_list=new[: arcs.n_rec])
-        return m, arcs
 
     def compact(self, arcs: ArchiveSet, removed_pos, pos_base: int, new_ivs=None) -> ArchiveSet:
         """A sweep's ``removed_pos`` (``HipHashesMap.sweep``) -> the compacted archives.  The

@@ -39,7 +39,10 @@
 // 817-882, 897-940, 595-648, 656-688) claim straight from slot images: validate (one wave per
 // slot), then apply (a wave per kWalkPart pairs).  recount is the same walk pointed at a shadow
 // count in each slot's spare bytes, followed by a count / scan / emit over the table; load and
-// export are the way in and out with the caller's positions.
+// export are the way in and out with the caller's positions.  addref_slots (writeSparseDataChunk,
+// StorageServiceImpl.java:275-382) is the walk once more, all or nothing per slot: validate, a
+// check pass that probes and counts each slot's misses, an apply pass that runs only where there
+// were none.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +51,7 @@
 #include <mutex>
 
 #include "../../include/sdfs_index.h"
+#include "../../include/sdfs_ingest.h"
 #include "call_support.h"
 #include "cdc_internal.h"
 #include "store_format.h"
@@ -431,6 +435,12 @@ struct WalkArgs {
     uint64_t* counts;    // [0] applied, [1] missed, [2] corrupt slots
     uint64_t* nonempty;  // selected slots with at least one pair, or NULL
     uint32_t parts;      // waves per slot in the apply pass
+    // addref_slots alone
+    const uint8_t* inserted;  // [nslots x pair_stride] or NULL: pairs that are skipped entirely
+    uint32_t pair_stride;
+    uint32_t* miss_list;      // [miss_cap x 2] {request, pair}
+    uint64_t miss_cap;
+    uint64_t* acounts;        // [0] added, [1] missed, [2] skipped, [3] accepted, [4] rejected, [5] misses listed
 };
 
 // N 32-bit words from p, whatever its alignment: aligned loads realigned by a byte shift.  Every
@@ -485,11 +495,20 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_validate_kernel(WalkArgs
     }
 }
 
-// HW: words of a pair's hash (8 = SHA-256, 4 = MD5).  SHADOW: recount (+1 on the entry's shadow
-// count) instead of claim (delta on its count).
-template <int HW, bool SHADOW>
+// what the apply pass does with a pair whose digest is held at its hashloc
+enum : int {
+    kWalkClaim,        // claim_slots: delta on the entry's count
+    kWalkShadow,       // recount: +1 on the entry's shadow count
+    kWalkAddrefCheck,  // addref_slots, first pass: nothing moves; the slot's misses are counted and listed
+    kWalkAddrefApply,  // addref_slots, second pass: +1 on the entry's count, in the slots that had no miss
+};
+
+// HW: words of a pair's hash (8 = SHA-256, 4 = MD5).
+template <int HW, int MODE>
 __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a, IndexSlot* table, uint64_t cmask,
                                                                      int64_t delta) {
+    constexpr bool SHADOW = MODE == kWalkShadow;
+    constexpr bool ADDREF = MODE == kWalkAddrefCheck || MODE == kWalkAddrefApply;
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t unit = (uint64_t)blockIdx.x * (kWalkThreads / 64) + (threadIdx.x >> 6);
     const uint64_t s = unit / a.parts;
@@ -498,10 +517,12 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
     const uint32_t n = meta & ~kWalkUnsorted;
     const uint32_t i0 = (uint32_t)(unit % a.parts) * kWalkPart;
     if (i0 >= n) return;
+    // the check pass has finished: a slot with a miss moves no count, in any of its waves
+    if (MODE == kWalkAddrefApply && a.missed[s] != 0) return;
     const uint32_t i1 = min(n, i0 + kWalkPart);
     constexpr uint32_t hl = HW * 4;
     const uint8_t* img = a.map + s * a.slot_bytes;
-    uint32_t applied = 0, missed = 0;
+    uint32_t applied = 0, missed = 0, skipped = 0;
     for (uint32_t ib = i0; ib < i1; ib += 64) {  // the same trip count for every lane of the wave
         const uint32_t i = ib + lane;
         bool on = i < i1;
@@ -510,6 +531,10 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
             bool dead = false;
             for (uint32_t j = i + 1; j < n; j++) dead |= get_be32(pair_fields(img, j, hl) + kPairPosAt) == ps;
             on = !dead;
+        }
+        if (ADDREF && on && a.inserted && a.inserted[s * a.pair_stride + i]) {  // neither probed nor counted
+            on = false;
+            skipped++;
         }
         bool hit = false;
         uint32_t at = 0;  // the entry's table slot (slots <= 2^31)
@@ -539,7 +564,15 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
         const unsigned long long hits = __ballot(hit);
         const bool head = hit && (lane == 0 || !((hits >> (lane - 1)) & 1) || prev_at != at);
         const unsigned long long stops = __ballot(head) | ~hits;  // lanes at which a run ends
-        if (head) {
+        if (MODE == kWalkAddrefCheck) {
+            if (on && !hit) {
+                const unsigned long long k = atomicAdd(reinterpret_cast<unsigned long long*>(&a.acounts[5]), 1ull);
+                if (k < a.miss_cap) {
+                    a.miss_list[2 * k] = (uint32_t)s;
+                    a.miss_list[2 * k + 1] = i;
+                }
+            }
+        } else if (head) {
             const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
             const unsigned long long k = above ? (unsigned long long)__ffsll((long long)above) : 64ull - lane;
             IndexSlot& e = table[at];
@@ -553,6 +586,21 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
     for (int o = 32; o > 0; o >>= 1) {
         applied += __shfl_xor(applied, o);
         missed += __shfl_xor(missed, o);
+        if (ADDREF) skipped += __shfl_xor(skipped, o);
+    }
+    if (ADDREF) {
+        if (lane != 0) return;
+        unsigned long long* c = reinterpret_cast<unsigned long long*>(a.acounts);
+        if (MODE == kWalkAddrefCheck) {
+            if (missed) {
+                atomicAdd(&c[1], (unsigned long long)missed);
+                atomicAdd(&a.missed[s], missed);
+            }
+            if (skipped) atomicAdd(&c[2], (unsigned long long)skipped);
+        } else if (applied) {
+            atomicAdd(&c[0], (unsigned long long)applied);
+        }
+        return;
     }
     if (lane == 0) {
         if (applied) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[0]), (unsigned long long)applied);
@@ -575,6 +623,26 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_free_kernel(uint8_t* map
     uint4* v = reinterpret_cast<uint4*>(p + head);
     for (uint32_t i = threadIdx.x; i < nvec; i += kWalkThreads) v[i] = make_uint4(0, 0, 0, 0);
     for (uint32_t i = head + nvec * 16 + threadIdx.x; i < slot_bytes; i += kWalkThreads) p[i] = 0;
+}
+
+// addref_slots, last: a request's status from its parse and its misses; the batch's totals
+__global__ __launch_bounds__(kIxThreads) void ix_addref_finish_kernel(WalkArgs a) {
+    const uint64_t s = (uint64_t)blockIdx.x * kIxThreads + threadIdx.x;
+    uint32_t ok = 0, bad = 0;
+    if (s < a.nslots) {
+        uint32_t st = a.status[s];
+        if (!st && a.missed[s]) st = SDFS_CDC_INGEST_EMISSED;
+        a.status[s] = st;
+        ok = st == 0;
+        bad = st != 0;
+    }
+    const uint32_t nok = (uint32_t)__popcll(__ballot(ok)), nbad = (uint32_t)__popcll(__ballot(bad));
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* c = reinterpret_cast<unsigned long long*>(a.acounts);
+        if (nok) atomicAdd(&c[3], (unsigned long long)nok);
+        if (nbad) atomicAdd(&c[4], (unsigned long long)nbad);
+    }
+    if (s == 0 && a.acounts[5] > a.miss_cap) a.acounts[5] = a.miss_cap;  // the check pass has finished
 }
 
 __global__ __launch_bounds__(kIxThreads) void ix_shadow_zero_kernel(IndexSlot* table, uint64_t slots) {
@@ -935,20 +1003,33 @@ static int check_walk(const sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t n
 }
 
 // Validate, then apply, on s.  a.meta is filled in here; the caller has zeroed a.counts.
-template <bool SHADOW>
+template <int MODE>
+static void launch_apply(sdfs_cdc_index* ix, hipStream_t s, const WalkArgs& a, int64_t delta) {
+    constexpr uint32_t wpb = kWalkThreads / 64;
+    const dim3 grid((uint32_t)((a.nslots * a.parts + wpb - 1) / wpb));
+    if (a.hash_len == 32)
+        hipLaunchKernelGGL((ix_walk_apply_kernel<8, MODE>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
+                           ix->slots - 1, delta);
+    else
+        hipLaunchKernelGGL((ix_walk_apply_kernel<4, MODE>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
+                           ix->slots - 1, delta);
+}
+
+template <int MODE>
 static int launch_walk(sdfs_cdc_index* ix, hipStream_t s, Scratch& sc, WalkArgs a, int64_t delta) {
     a.parts = std::max<uint32_t>(1, (pair_cap(a.slot_bytes, a.hash_len) + kWalkPart - 1) / kWalkPart);
     SDFS_TRY(sc.get(&a.meta, (size_t)a.nslots));
     constexpr uint32_t wpb = kWalkThreads / 64;
     hipLaunchKernelGGL(ix_walk_validate_kernel, dim3((uint32_t)((a.nslots + wpb - 1) / wpb)), dim3(kWalkThreads), 0, s,
                        a);
-    const dim3 grid((uint32_t)((a.nslots * a.parts + wpb - 1) / wpb));
-    if (a.hash_len == 32)
-        hipLaunchKernelGGL((ix_walk_apply_kernel<8, SHADOW>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
-                           ix->slots - 1, delta);
-    else
-        hipLaunchKernelGGL((ix_walk_apply_kernel<4, SHADOW>), grid, dim3(kWalkThreads), 0, s, a, ix->table.p,
-                           ix->slots - 1, delta);
+    if (MODE == kWalkAddrefCheck) {  // check, then apply where nothing was missed, then the statuses
+        launch_apply<kWalkAddrefCheck>(ix, s, a, delta);
+        launch_apply<kWalkAddrefApply>(ix, s, a, delta);
+        hipLaunchKernelGGL(ix_addref_finish_kernel, dim3((uint32_t)((a.nslots + kIxThreads - 1) / kIxThreads)),
+                           dim3(kIxThreads), 0, s, a);
+    } else {
+        launch_apply<MODE>(ix, s, a, delta);
+    }
     IX_TRY(hipGetLastError());
     return SDFS_CDC_OK;
 }
@@ -969,13 +1050,42 @@ int sdfs_cdc_index_claim_slots(sdfs_cdc_index* ix, uint8_t* d_map, uint64_t nslo
     if (nslots) {
         Scratch sc(s);
         WalkArgs a{d_map, nslots, slot_bytes, hash_len, d_sel, d_slot_status, d_slot_missed, nullptr, d_counts,
-                   d_counts + 3, 1};
-        if (const int rc = launch_walk<false>(ix, s, sc, a, delta)) return rc;
+                   d_counts + 3, 1, nullptr, 0, nullptr, 0, nullptr};
+        if (const int rc = launch_walk<kWalkClaim>(ix, s, sc, a, delta)) return rc;
         if (free_slots) {
             hipLaunchKernelGGL(ix_walk_free_kernel, dim3((uint32_t)nslots), dim3(kWalkThreads), 0, s, d_map, slot_bytes,
                                d_sel, d_slot_status);
             IX_TRY(hipGetLastError());
         }
+    }
+    IX_TRY(ix->order.release(s));
+    return SDFS_CDC_OK;
+}
+
+int sdfs_cdc_index_addref_slots(sdfs_cdc_index* ix, const uint8_t* d_req, uint64_t nreq, uint32_t slot_bytes,
+                                uint32_t hash_len, const uint8_t* d_inserted, uint32_t pair_stride,
+                                uint32_t* d_status, uint32_t* d_req_missed, uint32_t* d_miss_list, uint64_t miss_cap,
+                                uint64_t* d_counts, void* stream) {
+    if (const int rc = check_walk(ix, d_req, nreq, slot_bytes, hash_len, d_status, d_counts)) return rc;
+    if (!d_req_missed) return fail_status(SDFS_CDC_EINVAL, "null req_missed");
+    if (miss_cap && !d_miss_list) return fail_status(SDFS_CDC_EINVAL, "null miss list");
+    if (d_inserted && pair_stride < pair_cap(slot_bytes, hash_len))
+        return fail_status(SDFS_CDC_EINVAL, "pair_stride %u: a slot of %u bytes holds up to %u pairs", pair_stride,
+                           slot_bytes, pair_cap(slot_bytes, hash_len));
+    std::lock_guard<std::mutex> lk(ix->mu);
+    IX_TRY(hipSetDevice(ix->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    IX_TRY(ix->order.acquire(s));
+    ix->last = s;
+    IX_TRY(hipMemsetAsync(d_counts, 0, 6 * sizeof(uint64_t), s));
+    if (nreq) {
+        Scratch sc(s);
+        uint64_t* vcounts = nullptr;  // the validation's own three counts
+        SDFS_TRY(sc.get(&vcounts, 3));
+        IX_TRY(hipMemsetAsync(vcounts, 0, 3 * sizeof(uint64_t), s));
+        WalkArgs a{d_req, nreq, slot_bytes, hash_len, nullptr, d_status, d_req_missed, nullptr, vcounts, nullptr, 1,
+                   d_inserted, pair_stride, d_miss_list, miss_cap, d_counts};
+        if (const int rc = launch_walk<kWalkAddrefCheck>(ix, s, sc, a, 1)) return rc;
     }
     IX_TRY(ix->order.release(s));
     return SDFS_CDC_OK;
@@ -999,8 +1109,8 @@ int sdfs_cdc_index_recount(sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t ns
     if (nslots) {
         Scratch sc(s);
         WalkArgs a{d_map, nslots, slot_bytes, hash_len, d_sel, d_slot_status, d_slot_missed, nullptr, d_counts,
-                   nullptr, 1};
-        if (const int rc = launch_walk<true>(ix, s, sc, a, 0)) return rc;
+                   nullptr, 1, nullptr, 0, nullptr, 0, nullptr};
+        if (const int rc = launch_walk<kWalkShadow>(ix, s, sc, a, 0)) return rc;
     }
     const uint32_t nb = (uint32_t)((ix->slots + kRankBlock - 1) / kRankBlock);
     hipLaunchKernelGGL(ix_flag_count_kernel<kFlagMismatch>, dim3(nb), dim3(kRankBlock), 0, s, ix->table.p, ix->slots,
