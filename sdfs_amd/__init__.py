@@ -23,8 +23,10 @@ from .extent import copy_extents, rewrite_blocks, split_extent  # noqa: F401
 from .mapfile import close_map, index_map, open_map, snapshot, snapshot_compressed, trim, truncate, vanish  # noqa: F401
 from .lz4_stream import HipLz4BlockStream, compressFile, decompressFile, xxh32  # noqa: F401
 from .ingest import ChunkBatch, HipChunkIngest, SparseWrites, pack_entries  # noqa: F401
+from .replicate import HipFileImport, ImportResult, SourceVolume  # noqa: F401
 
 __all__ = [
+    "HipFileImport", "ImportResult", "SourceVolume",
     "index_map", "snapshot", "vanish", "trim", "truncate", "close_map", "open_map", "snapshot_compressed",
     "HipChunkIngest", "ChunkBatch", "SparseWrites", "pack_entries",
     "HipLz4BlockStream", "compressFile", "decompressFile", "xxh32",

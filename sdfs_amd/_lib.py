@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
                                for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h",
-                                         "sdfs_extent.h", "sdfs_lz4_stream.h", "sdfs_ingest.h")]
+                                         "sdfs_extent.h", "sdfs_lz4_stream.h", "sdfs_ingest.h", "sdfs_import.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -228,6 +228,18 @@ class IngestPlan(ctypes.Structure):
 INGEST_EMPTY, INGEST_EBOUNDS, INGEST_EDECODE, INGEST_EHASH, INGEST_EMISSED = 1, 2, 4, 8, 16
 INGEST_NONE, INGEST_TILE, INGEST_COPY_SPAN = 0xFFFFFFFF, 1024, 65536
 
+class ImportWork(ctypes.Structure):
+    """``sdfs_cdc_import_work`` (include/sdfs_import.h): what the calls of one import share, device pointers."""
+
+    _fields_ = [("hashes", ctypes.c_void_p), ("src_hashloc", ctypes.c_void_p), ("counting", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("req_pairs", ctypes.c_void_p), ("req_missed", ctypes.c_void_p),
+                ("pair_fetch", ctypes.c_void_p), ("pair_rec", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+# SDFS_CDC_IMPORT_*
+IMPORT_EMISSING, IMPORT_EFETCH, IMPORT_EHASH = 32, 64, 128
+IMPORT_NONE, IMPORT_BLOCK, IMPORT_SPAN = 0xFFFFFFFF, 1024, 16384
+
 # (name, restype, argtypes) for every entry point of include/sdfs_cdc.h
 _P = ctypes.POINTER
 _u8p, _u32p, _u64p, _vp = _P(ctypes.c_uint8), _P(ctypes.c_uint32), _P(ctypes.c_uint64), ctypes.c_void_p
@@ -409,6 +421,19 @@ SIGNATURES = {
     "sdfs_cdc_ingest_chunks_records": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), _P(IngestPlan), _vp, _vp, _vp]),
     "sdfs_cdc_ingest_chunks_results": (ctypes.c_int, [ctypes.c_int, _P(IngestBatch), _P(IngestPlan), _vp, _vp,
                                                       ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    # include/sdfs_import.h
+    "sdfs_cdc_import_pairs": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, _P(ImportWork), _vp]),
+    "sdfs_cdc_import_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, _P(ImportWork), _vp,
+                                            ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, ctypes.c_uint32, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdfs_cdc_import_records": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                               _P(ImportWork), _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp]),
+    "sdfs_cdc_import_install": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, _P(ImportWork), _vp, _vp, _vp, ctypes.c_uint32, _vp,
+                                               ctypes.c_uint64, _vp, _vp]),
+    "sdfs_cdc_import_check_dests": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64]),
 }
 
 _lib = None

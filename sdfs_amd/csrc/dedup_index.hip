@@ -443,21 +443,6 @@ struct WalkArgs {
     uint64_t* acounts;        // [0] added, [1] missed, [2] skipped, [3] accepted, [4] rejected, [5] misses listed
 };
 
-// N 32-bit words from p, whatever its alignment: aligned loads realigned by a byte shift.  Every
-// word loaded holds at least one of the bytes asked for.
-template <int N>
-__device__ __forceinline__ void load_words(const uint8_t* p, uint32_t (&w)[N]) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const uint32_t r = (uint32_t)(a & 3);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(a - r);
-    uint32_t t[N + 1];
-#pragma unroll
-    for (int i = 0; i < N; i++) t[i] = q[i];
-    t[N] = r ? q[N] : 0u;
-#pragma unroll
-    for (int i = 0; i < N; i++) w[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], r);
-}
-
 __global__ __launch_bounds__(kWalkThreads) void ix_walk_validate_kernel(WalkArgs a) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t s = (uint64_t)blockIdx.x * (kWalkThreads / 64) + (threadIdx.x >> 6);

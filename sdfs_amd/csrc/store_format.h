@@ -71,6 +71,21 @@ __device__ __forceinline__ B* pair_fields(B* img, uint32_t i, uint32_t hash_len)
     return slot_pair(img, i, hash_len) + hash_len;
 }
 
+// N 32-bit words from p, whatever its alignment: aligned loads realigned by a byte shift.  Every
+// word loaded holds at least one of the bytes asked for.
+template <int N>
+__device__ __forceinline__ void load_words(const uint8_t* p, uint32_t (&w)[N]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const uint32_t r = (uint32_t)(a & 3);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(a - r);
+    uint32_t t[N + 1];
+#pragma unroll
+    for (int i = 0; i < N; i++) t[i] = q[i];
+    t[N] = r ? q[N] : 0u;
+#pragma unroll
+    for (int i = 0; i < N; i++) w[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], r);
+}
+
 // pair i from its six fields (byte stores: records start at odd offsets)
 __device__ __forceinline__ void put_pair_record(uint8_t* img, uint32_t i, uint32_t hash_len, const uint8_t* hash,
                                                 uint64_t hashloc, uint32_t len, uint32_t pos, uint32_t offset,
