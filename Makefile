@@ -9,10 +9,10 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-functi
 CSRC := sdfs_amd/csrc
 LIB := sdfs_amd/libsdfs_cdc.so
 TUNING_LIB := sdfs_amd/libsdfs_cdc_tuning.so
-SRCS := cdc_kernels cdc_engine dedup_index lz4_kernels map_emit aes_kernels read_path archive_pack store_open map_merge lz4_stream client_ingest map_import
+SRCS := cdc_kernels cdc_engine dedup_index lz4_kernels map_emit aes_kernels read_path archive_pack store_open map_merge lz4_stream client_ingest map_import write_path
 OBJS := $(SRCS:%=build/%.o)
 TUNING_OBJS := $(SRCS:%=build/tuning/%.o) build/tuning/cdc_sweep.o build/tuning/cdc_sweep_r3.o
-HDRS := $(CSRC)/cdc_internal.h $(CSRC)/cdc_device.h $(CSRC)/host_queue.h $(CSRC)/engine_share.h $(CSRC)/stream_order.h $(CSRC)/store_format.h $(CSRC)/call_support.h $(CSRC)/block_scan.h $(CSRC)/lz4_decode.h $(CSRC)/read_split.h $(wildcard include/*.h)
+HDRS := $(CSRC)/cdc_internal.h $(CSRC)/cdc_device.h $(CSRC)/host_queue.h $(CSRC)/engine_share.h $(CSRC)/stream_order.h $(CSRC)/store_format.h $(CSRC)/call_support.h $(CSRC)/block_scan.h $(CSRC)/lz4_decode.h $(CSRC)/read_split.h $(CSRC)/write_split.h $(wildcard include/*.h)
 
 all: $(LIB) tuning tools oracle buildinfo
 

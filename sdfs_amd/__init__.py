@@ -24,8 +24,10 @@ from .mapfile import close_map, index_map, open_map, snapshot, snapshot_compress
 from .lz4_stream import HipLz4BlockStream, compressFile, decompressFile, xxh32  # noqa: F401
 from .ingest import ChunkBatch, HipChunkIngest, SparseWrites, pack_entries  # noqa: F401
 from .replicate import HipFileImport, ImportResult, SourceVolume  # noqa: F401
+from .write import HipFileWriter, WriteResult, split_writes  # noqa: F401
 
 __all__ = [
+    "HipFileWriter", "WriteResult", "split_writes",
     "HipFileImport", "ImportResult", "SourceVolume",
     "index_map", "snapshot", "vanish", "trim", "truncate", "close_map", "open_map", "snapshot_compressed",
     "HipChunkIngest", "ChunkBatch", "SparseWrites", "pack_entries",

@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SDFS_CDC_LIB") or DEFAULT_LIB
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "sdfs_cdc.h")
 HEADER_PATHS = [HEADER_PATH] + [os.path.join(os.path.dirname(HERE), "include", h)
                                for h in ("sdfs_index.h", "sdfs_lz4.h", "sdfs_meta.h", "sdfs_aes.h", "sdfs_read.h", "sdfs_archive.h", "sdfs_store.h",
-                                         "sdfs_extent.h", "sdfs_lz4_stream.h", "sdfs_ingest.h", "sdfs_import.h")]
+                                         "sdfs_extent.h", "sdfs_lz4_stream.h", "sdfs_ingest.h", "sdfs_import.h", "sdfs_write.h")]
 
 OK, EINVAL, ECAP, EHIP, ENOMEM, ENODEV = 0, -1, -2, -3, -4, -5
 FLAG_DIRECT = 1  # SDFS_CDC_FLAG_DIRECT: no coalescing of concurrent getChunks/getHash calls
@@ -240,6 +240,22 @@ class ImportWork(ctypes.Structure):
 IMPORT_EMISSING, IMPORT_EFETCH, IMPORT_EHASH = 32, 64, 128
 IMPORT_NONE, IMPORT_BLOCK, IMPORT_SPAN = 0xFFFFFFFF, 1024, 16384
 
+class WritePlan(ctypes.Structure):
+    """``sdfs_cdc_write_plan`` (include/sdfs_write.h): the write split's outputs, host pointers."""
+
+    _fields_ = [("piece_cap", ctypes.c_uint32), ("run_cap", ctypes.c_uint32), ("row_cap", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("piece_row", ctypes.c_void_p), ("piece_start", ctypes.c_void_p),
+                ("piece_len", ctypes.c_void_p), ("piece_req", ctypes.c_void_p), ("piece_src_off", ctypes.c_void_p),
+                ("run_row", ctypes.c_void_p), ("run_pos", ctypes.c_void_p), ("run_len", ctypes.c_void_p),
+                ("run_first_piece", ctypes.c_void_p), ("run_n_pieces", ctypes.c_void_p), ("row_slot", ctypes.c_void_p),
+                ("row_full", ctypes.c_void_p), ("n_pieces", ctypes.c_uint64), ("n_runs", ctypes.c_uint64),
+                ("n_rows", ctypes.c_uint64)]
+
+
+# SDFS_CDC_WRITE_*
+WRITE_SLOT, WRITE_READ, WRITE_BOUNDS = 1, 2, 4
+WRITE_SPAN = 65536
+
 # (name, restype, argtypes) for every entry point of include/sdfs_cdc.h
 _P = ctypes.POINTER
 _u8p, _u32p, _u64p, _vp = _P(ctypes.c_uint8), _P(ctypes.c_uint32), _P(ctypes.c_uint64), ctypes.c_void_p
@@ -434,6 +450,14 @@ SIGNATURES = {
                                                ctypes.c_uint32, _P(ImportWork), _vp, _vp, _vp, ctypes.c_uint32, _vp,
                                                ctypes.c_uint64, _vp, _vp]),
     "sdfs_cdc_import_check_dests": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64]),
+    # include/sdfs_write.h
+    "sdfs_cdc_write_split": (ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                            _vp, _vp, _P(WritePlan)]),
+    "sdfs_cdc_write_stage": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                            ctypes.c_uint32, _vp, ctypes.c_uint64, _vp, _vp, ctypes.c_uint32, _vp, _vp]),
+    "sdfs_cdc_map_inserts_from_runs": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _P(DevOut), _vp, _vp,
+                                                      _vp, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _P(Inserts),
+                                                      ctypes.c_uint64, _vp, _vp]),
 }
 
 _lib = None
