@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kPlanThreads) void archive_plan_kernel(PlanArgs a) 
     for (uint64_t i0 = 0; i0 < n; i0 += kPlanThreads) {
         const uint64_t i = i0 + t;
         const uint64_t v = i < n ? (uint64_t)unit + a.rec_len[i] : 0;
-        const uint64_t inc = wave_inclusive_scan(v, lane);
+        const uint64_t inc = wave_inclusive_scan(v, lane);  // its own scan text: see block_exclusive_scan_1024
         if (lane == 63) wsum[wave] = inc;
         __syncthreads();
         uint64_t before = carry, tile = 0;
@@ -504,8 +504,7 @@ __global__ __launch_bounds__(256) void compact_count_kernel(SelectArgs a) {
     const uint32_t size = min(a.old_sizes ? a.old_sizes[arc] : a.old_stride, a.old_stride);
     uint32_t c = 0, r;
     for (uint32_t s = t; s < size; s += 256) c += slot_kept(a, arc, s, size, r);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum(c);
     if ((t & 63) == 0) ws[t >> 6] = c;
     __syncthreads();
     if (t == 0) a.live[arc] = ws[0] + ws[1] + ws[2] + ws[3];

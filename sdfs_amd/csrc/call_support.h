@@ -1,6 +1,6 @@
 // call_support.h — what every entry point of the store layer does around its launches: the
 // device, per-call scratch, the mapping of HIP errors to C-ABI codes, the hash_len checks and the
-// live count of a batch.  Not part of the C-ABI.
+// live count of a batch, the 64-bit add of its counters.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,6 +88,12 @@ int check_header(uint32_t header_bytes) {
 // records of a batch whose count may live on the device
 __device__ __forceinline__ uint64_t live_count(const uint32_t* count, uint64_t n_max) {
     return count ? min<uint64_t>(*count, n_max) : n_max;
+}
+
+// a device-scope 64-bit add, returning the word's value before it (HIP's atomicAdd takes unsigned
+// long long; the counters are uint64_t words)
+__device__ __forceinline__ uint64_t add64(uint64_t* p, uint64_t v) {
+    return atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
 
 }  // namespace

@@ -48,8 +48,8 @@ __device__ __forceinline__ uint32_t classify(const Batch& b, uint64_t i, uint32_
 // step, so the prefix is over the whole batch in entry order.
 __global__ __launch_bounds__(kTile) void ingest_plan_kernel(Batch b, Plan p, uint32_t chunk_length,
                                                             uint64_t stage_cap) {
-    __shared__ uint64_t part[kTile];
-    uint64_t byte_carry = 0, dec_carry = 0;
+    __shared__ uint64_t lds[16];
+    uint64_t byte_carry = 0, dec_carry = 0, total;
     for (uint64_t t0 = 0; t0 < b.n; t0 += kTile) {
         const uint64_t i = t0 + threadIdx.x;
         uint32_t st = SDFS_CDC_INGEST_EBOUNDS, raw = 0;
@@ -59,17 +59,15 @@ __global__ __launch_bounds__(kTile) void ingest_plan_kernel(Batch b, Plan p, uin
             raw = st ? 0 : b.raw_len[i];
             dec = !st && b.compressed[i];
         }
-        const uint64_t at = byte_carry + block_inclusive_scan_1024<uint64_t>(raw, part) - raw;
-        byte_carry += part[kTile - 1];
-        __syncthreads();
+        const uint64_t at = byte_carry + block_exclusive_scan_1024<uint64_t>(raw, lds, total);
+        byte_carry += total;
         // a chunk that would end past the staging area is left out; those before it keep their places
         if (!st && (at > stage_cap || raw > stage_cap - at)) {
             st = SDFS_CDC_INGEST_EBOUNDS;
             dec = false;
         }
-        const uint64_t k = dec_carry + block_inclusive_scan_1024<uint64_t>(dec ? 1 : 0, part) - (dec ? 1 : 0);
-        dec_carry += part[kTile - 1];
-        __syncthreads();
+        const uint64_t k = dec_carry + block_exclusive_scan_1024<uint64_t>(dec ? 1 : 0, lds, total);
+        dec_carry += total;
         if (i < b.n) {
             p.status[i] = st;
             p.stage_off[i] = st ? 0 : at;
@@ -150,14 +148,13 @@ __global__ __launch_bounds__(256) void ingest_compare_kernel(Batch b, Plan p, co
 
 // One block, as the plan: the accepted entries' ranks in entry order.
 __global__ __launch_bounds__(kTile) void ingest_records_kernel(Batch b, Plan p, uint8_t* records, uint32_t* count) {
-    __shared__ uint32_t part[kTile];
-    uint32_t carry = 0;
+    __shared__ uint32_t lds[16];
+    uint32_t carry = 0, total;
     for (uint64_t t0 = 0; t0 < b.n; t0 += kTile) {
         const uint64_t i = t0 + threadIdx.x;
         const uint32_t on = i < b.n && p.status[i] == 0 ? 1u : 0u;
-        const uint32_t r = carry + block_inclusive_scan_1024<uint32_t>(on, part) - on;
-        carry += part[kTile - 1];
-        __syncthreads();
+        const uint32_t r = carry + block_exclusive_scan_1024<uint32_t>(on, lds, total);
+        carry += total;
         if (i >= b.n) continue;
         p.rec_of[i] = on ? r : SDFS_CDC_INGEST_NONE;
         if (!on) continue;

@@ -37,7 +37,7 @@
 //
 // Whole-map-file walks (LongByteArrayMap.vanish / index / trim / truncate, LongByteArrayMap.java:
 // 817-882, 897-940, 595-648, 656-688) claim straight from slot images: validate (one wave per
-// slot), then apply (a wave per kWalkPart pairs).  recount is the same walk pointed at a shadow
+// slot), then apply (a wave per kSlotPart pairs).  recount is the same walk pointed at a shadow
 // count in each slot's spare bytes, followed by a count / scan / emit over the table; load and
 // export are the way in and out with the caller's positions.  addref_slots (writeSparseDataChunk,
 // StorageServiceImpl.java:275-382) is the walk once more, all or nothing per slot: validate, a
@@ -52,6 +52,7 @@
 
 #include "../../include/sdfs_index.h"
 #include "../../include/sdfs_ingest.h"
+#include "block_scan.h"
 #include "call_support.h"
 #include "cdc_internal.h"
 #include "store_format.h"
@@ -95,15 +96,11 @@ __device__ __forceinline__ bool eq4(const uint4& x, const uint4& y) {
     return ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) == 0;
 }
 
-__device__ __forceinline__ uint32_t batch_count(const uint32_t* d_count, uint64_t n_max) {
-    return d_count ? (uint32_t)min<uint64_t>(*d_count, n_max) : (uint32_t)n_max;
-}
-
 // 1. group equal fingerprints of the batch; ltab holds the smallest record index of each group
 __global__ __launch_bounds__(kIxThreads) void ix_group_kernel(const uint8_t* records, const uint32_t* d_count,
                                                               uint64_t n_max, uint32_t* ltab, uint32_t* lcount,
                                                               uint32_t lmask, uint32_t* lslot) {
-    const uint32_t n = batch_count(d_count, n_max);
+    const uint32_t n = (uint32_t)live_count(d_count, n_max);
     const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
     if (r >= n) return;
     uint4 a, b;
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_probe_kernel(const uint8_t* rec
                                                               const uint32_t* lcount, const uint32_t* lslot,
                                                               IndexSlot* table, uint64_t cmask, uint32_t stamp,
                                                               uint32_t* gidx, uint32_t* isnew, uint32_t* overflow) {
-    const uint32_t n = batch_count(d_count, n_max);
+    const uint32_t n = (uint32_t)live_count(d_count, n_max);
     const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
     if (r >= n) return;
     const uint32_t ls = lslot[r];
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_probe_kernel(const uint8_t* rec
         if (st == stamp) continue;  // inserted by this batch: a different fingerprint
         if (st == kTombstone) continue;  // swept: the chain goes on, the key is stale
         if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
-            atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)claims);
+            add64(&s.ref, claims);
             gidx[ls] = (uint32_t)h;
             isnew[r] = 0;
             return;
@@ -176,58 +173,22 @@ __global__ __launch_bounds__(kIxThreads) void ix_probe_kernel(const uint8_t* rec
     isnew[r] = 0;
 }
 
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* lds, uint32_t& total) {
-    // kRankBlock threads = 16 waves: wave-level inclusive scan, then a scan of the 16 wave sums
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= (uint32_t)o) x += y;
-    }
-    if (lane == 63) lds[wv] = x;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t w = threadIdx.x < kRankBlock / 64 ? lds[threadIdx.x] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(w, o);
-            if (lane >= (uint32_t)o) w += y;
-        }
-        if (threadIdx.x < kRankBlock / 64) lds[16 + threadIdx.x] = w;
-    }
-    __syncthreads();
-    total = lds[16 + kRankBlock / 64 - 1];
-    const uint32_t before = wv ? lds[16 + wv - 1] : 0;
-    const uint32_t res = before + x - v;
-    __syncthreads();
-    return res;
-}
-
 // 3. inserted records per block of kRankBlock records
 __global__ __launch_bounds__(kRankBlock) void ix_count_kernel(const uint32_t* d_count, uint64_t n_max,
                                                               const uint32_t* isnew, uint32_t* bsum) {
-    __shared__ uint32_t lds[64];
-    const uint32_t n = batch_count(d_count, n_max);
+    __shared__ uint32_t lds[16];
+    const uint32_t n = (uint32_t)live_count(d_count, n_max);
     const uint32_t r = blockIdx.x * kRankBlock + threadIdx.x;
     uint32_t total;
-    (void)block_exclusive_scan(r < n ? isnew[r] : 0u, lds, total);
+    (void)block_exclusive_scan_1024(r < n ? isnew[r] : 0u, lds, total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
 // 4. exclusive scan of the block counts (one block), batch total, running index size
 __global__ __launch_bounds__(kRankBlock) void ix_scan_kernel(uint32_t* bsum, uint32_t nblocks, uint64_t* new_count,
                                                              uint64_t* used) {
-    __shared__ uint32_t lds[64];
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += kRankBlock) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nblocks ? bsum[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, lds, total);
-        if (i < nblocks) bsum[i] = carry + ex;
-        carry += total;
-    }
+    __shared__ uint32_t lds[16];
+    const uint64_t carry = block_sums_to_bases(bsum, nblocks, lds);
     if (threadIdx.x == 0) {
         *new_count = carry;
         *used += carry;
@@ -240,12 +201,12 @@ __global__ __launch_bounds__(kRankBlock) void ix_assign_kernel(const uint32_t* d
                                                                const uint32_t* lslot, const uint32_t* gidx,
                                                                IndexSlot* table, uint64_t pos_base,
                                                                uint32_t* new_list) {
-    __shared__ uint32_t lds[64];
-    const uint32_t n = batch_count(d_count, n_max);
+    __shared__ uint32_t lds[16];
+    const uint32_t n = (uint32_t)live_count(d_count, n_max);
     const uint32_t r = blockIdx.x * kRankBlock + threadIdx.x;
     const uint32_t f = r < n ? isnew[r] : 0u;
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    const uint32_t ex = block_exclusive_scan_1024(f, lds, total);
     if (f) {
         const uint32_t rank = bbase[blockIdx.x] + ex;
         if (new_list) new_list[rank] = r;
@@ -260,7 +221,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_output_kernel(const uint32_t* d
                                                                const uint32_t* isnew, const uint32_t* lslot,
                                                                const uint32_t* gidx, const IndexSlot* table,
                                                                uint8_t* dup, uint64_t* hashloc) {
-    const uint32_t n = batch_count(d_count, n_max);
+    const uint32_t n = (uint32_t)live_count(d_count, n_max);
     const uint32_t r = blockIdx.x * kIxThreads + threadIdx.x;
     if (r >= n) return;
     if (dup) dup[r] = isnew[r] ? 0 : 1;
@@ -313,7 +274,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_claim_kernel(const uint8_t* dig
         if (eq4(s.key[0], a) && eq4(s.key[1], b)) {
             const uint64_t pos = s.pos;
             if (want == ~0ull || want == pos) {
-                atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)delta[i]);
+                add64(&s.ref, delta[i]);
                 rp = pos;
             }
             break;
@@ -331,13 +292,13 @@ __device__ __forceinline__ uint32_t slot_is_dead(const IndexSlot* table, uint64_
 // word, and the emit pass does not have to stream the table a second time
 __global__ __launch_bounds__(kRankBlock) void ix_sweep_count_kernel(const IndexSlot* table, uint64_t slots,
                                                                     uint32_t* bsum, unsigned long long* dead) {
-    __shared__ uint32_t lds[64];
+    __shared__ uint32_t lds[16];
     const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
     const uint32_t f = slot_is_dead(table, slots, i);
     const unsigned long long m = __ballot(f);
     if ((threadIdx.x & 63) == 0) dead[i >> 6] = m;
     uint32_t total;
-    (void)block_exclusive_scan(f, lds, total);
+    (void)block_exclusive_scan_1024(f, lds, total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -345,16 +306,8 @@ __global__ __launch_bounds__(kRankBlock) void ix_sweep_count_kernel(const IndexS
 // device's live and tombstone counts follow
 __global__ __launch_bounds__(kRankBlock) void ix_sweep_scan_kernel(uint32_t* bsum, uint32_t nblocks, uint64_t cap,
                                                                    uint64_t* counts, uint64_t* used) {
-    __shared__ uint32_t lds[64];
-    uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += kRankBlock) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nblocks ? bsum[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, lds, total);
-        if (i < nblocks) bsum[i] = (uint32_t)carry + ex;  // dead entries <= slots <= 2^31
-        carry += total;
-    }
+    __shared__ uint32_t lds[16];
+    const uint64_t carry = block_sums_to_bases(bsum, nblocks, lds);  // dead entries <= slots <= 2^31
     if (threadIdx.x == 0) {
         const uint64_t removed = carry < cap ? carry : cap;
         counts[0] = removed;
@@ -369,11 +322,11 @@ __global__ __launch_bounds__(kRankBlock) void ix_sweep_emit_kernel(IndexSlot* ta
                                                                    const uint32_t* bbase,
                                                                    const unsigned long long* dead, uint64_t cap,
                                                                    uint8_t* removed_digests, uint64_t* removed_pos) {
-    __shared__ uint32_t lds[64];
+    __shared__ uint32_t lds[16];
     const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
     const uint32_t f = (uint32_t)(dead[i >> 6] >> (threadIdx.x & 63)) & 1u;  // set only for i < slots
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    const uint32_t ex = block_exclusive_scan_1024(f, lds, total);
     if (!f) return;
     const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
     if (rank >= cap) return;
@@ -410,18 +363,15 @@ __global__ __launch_bounds__(kIxThreads) void ix_rebuild_kernel(const IndexSlot*
 
 // ---------------------------------------------------------------------------- map-file walks
 //
-// claim_slots and recount read HashLocPairs straight from slot images (store_format.h), by the
-// rule of map_parse_kernel (read_path.hip).  Validation is a kernel of its own (one wave per
-// slot): it settles every slot's status and pair count before any count moves.  The apply pass
-// gives a wave kWalkPart pairs of one slot, so a slot of thousands of pairs spreads over many
-// waves; a lane realigns its pair's hash and hashloc from aligned dword loads (pairs start at
-// odd byte offsets) and probes; a run of neighbouring lanes that found the same entry adds once,
-// with one 64-bit device-scope atomic.  Integer adds commute: the outcome does not depend on the
-// schedule.
+// claim_slots and recount read HashLocPairs straight from slot images, accepted by
+// slot_walk_check (store_format.h).  Validation is a kernel of its own (one wave per slot): it
+// settles every slot's status and pair count before any count moves.  The apply pass gives a wave
+// kSlotPart pairs of one slot, so a slot of thousands of pairs spreads over many waves; a lane
+// takes its pair's key and hashloc (load_pair_key) and probes; a run of neighbouring lanes that
+// found the same entry adds once, with one 64-bit device-scope atomic.  Integer adds commute: the
+// outcome does not depend on the schedule.
 
-constexpr int kWalkThreads = 256;                 // four waves, each on its own slot (part)
-constexpr uint32_t kWalkPart = 256;               // pairs of one slot a wave of the apply pass takes
-constexpr uint32_t kWalkUnsorted = 0x80000000u;   // meta: the image's pos values are not strictly ascending
+constexpr int kWalkThreads = 256;  // four waves, each on its own slot (part)
 
 struct WalkArgs {
     const uint8_t* map;
@@ -431,7 +381,7 @@ struct WalkArgs {
     const uint8_t* sel;
     uint32_t* status;    // [nslots]
     uint32_t* missed;    // [nslots] or NULL
-    uint32_t* meta;      // [nslots] scratch: pairs to apply | kWalkUnsorted
+    uint32_t* meta;      // [nslots] scratch: slot_meta
     uint64_t* counts;    // [0] applied, [1] missed, [2] corrupt slots
     uint64_t* nonempty;  // selected slots with at least one pair, or NULL
     uint32_t parts;      // waves per slot in the apply pass
@@ -447,36 +397,14 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_validate_kernel(WalkArgs
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t s = (uint64_t)blockIdx.x * (kWalkThreads / 64) + (threadIdx.x >> 6);
     if (s >= a.nslots) return;  // wave-uniform, as is every branch below
-    const uint32_t hl = a.hash_len;
-    uint32_t status = 0, n = 0;
-    bool unsorted = false;
-    if (!a.sel || a.sel[s]) {
-        const uint8_t* img = a.map + s * a.slot_bytes;
-        const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
-        if (zlen > 0) {
-            if (slot_need((uint32_t)zlen, hl) > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;
-            else n = (uint32_t)zlen;
-        }
-        bool neg = false;
-        for (uint32_t i = lane; i < n; i += 64) {
-            const uint8_t* q = pair_fields(img, i, hl);
-            const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
-            neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
-                    (int32_t)get_be32(q + kPairNlenAt)) < 0;
-            if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hl) + kPairPosAt) >= ps;
-        }
-        if (__ballot(neg) != 0) {  // HashLocPair.checkCorrupt
-            status = SDFS_CDC_READ_CORRUPT;
-            n = 0;
-        }
-        unsorted = __ballot(unsorted) != 0;
-    }
+    SlotWalk w{0, 0, false};
+    if (!a.sel || a.sel[s]) w = slot_walk_check(a.map + s * a.slot_bytes, a.slot_bytes, a.hash_len, lane);
     if (lane == 0) {
-        a.status[s] = status;
+        a.status[s] = w.status;
         if (a.missed) a.missed[s] = 0;
-        a.meta[s] = n | (n && unsorted ? kWalkUnsorted : 0u);
-        if (status) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[2]), 1ull);
-        if (n && a.nonempty) atomicAdd(reinterpret_cast<unsigned long long*>(a.nonempty), 1ull);
+        a.meta[s] = slot_meta(w);
+        if (w.status) add64(&a.counts[2], 1);
+        if (w.n && a.nonempty) add64(a.nonempty, 1);
     }
 }
 
@@ -499,24 +427,19 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
     const uint64_t s = unit / a.parts;
     if (s >= a.nslots) return;  // wave-uniform
     const uint32_t meta = a.meta[s];
-    const uint32_t n = meta & ~kWalkUnsorted;
-    const uint32_t i0 = (uint32_t)(unit % a.parts) * kWalkPart;
+    const uint32_t n = slot_meta_pairs(meta);
+    const uint32_t i0 = (uint32_t)(unit % a.parts) * kSlotPart;
     if (i0 >= n) return;
     // the check pass has finished: a slot with a miss moves no count, in any of its waves
     if (MODE == kWalkAddrefApply && a.missed[s] != 0) return;
-    const uint32_t i1 = min(n, i0 + kWalkPart);
+    const uint32_t i1 = min(n, i0 + kSlotPart);
     constexpr uint32_t hl = HW * 4;
     const uint8_t* img = a.map + s * a.slot_bytes;
     uint32_t applied = 0, missed = 0, skipped = 0;
     for (uint32_t ib = i0; ib < i1; ib += 64) {  // the same trip count for every lane of the wave
         const uint32_t i = ib + lane;
         bool on = i < i1;
-        if (on && (meta & kWalkUnsorted)) {  // TreeMap.put: a later pair with the same pos replaces this one
-            const uint32_t ps = get_be32(pair_fields(img, i, hl) + kPairPosAt);
-            bool dead = false;
-            for (uint32_t j = i + 1; j < n; j++) dead |= get_be32(pair_fields(img, j, hl) + kPairPosAt) == ps;
-            on = !dead;
-        }
+        if (on && slot_meta_unsorted(meta)) on = !pair_superseded(img, i, n, hl);
         if (ADDREF && on && a.inserted && a.inserted[s * a.pair_stride + i]) {  // neither probed nor counted
             on = false;
             skipped++;
@@ -524,11 +447,9 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
         bool hit = false;
         uint32_t at = 0;  // the entry's table slot (slots <= 2^31)
         if (on) {
-            uint32_t w[HW + 2];  // hash | BE64 hashloc
-            load_words(slot_pair(img, i, hl), w);
-            const uint4 ka = make_uint4(w[0], w[1], w[2], w[3]);
-            const uint4 kb = HW == 8 ? make_uint4(w[HW - 4], w[HW - 3], w[HW - 2], w[HW - 1]) : make_uint4(0, 0, 0, 0);
-            const uint64_t hashloc = (uint64_t)__builtin_bswap32(w[HW]) << 32 | __builtin_bswap32(w[HW + 1]);
+            uint4 ka, kb;
+            uint64_t hashloc;
+            load_pair_key<HW>(img, i, ka, kb, hashloc);
             uint64_t h = mix64((uint64_t)ka.y << 32 | ka.x) & cmask;
             for (uint64_t step = 0; step <= cmask; step++, h = (h + 1) & cmask) {
                 const IndexSlot& e = table[h];
@@ -551,7 +472,7 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
         const unsigned long long stops = __ballot(head) | ~hits;  // lanes at which a run ends
         if (MODE == kWalkAddrefCheck) {
             if (on && !hit) {
-                const unsigned long long k = atomicAdd(reinterpret_cast<unsigned long long*>(&a.acounts[5]), 1ull);
+                const uint64_t k = add64(&a.acounts[5], 1);
                 if (k < a.miss_cap) {
                     a.miss_list[2 * k] = (uint32_t)s;
                     a.miss_list[2 * k + 1] = i;
@@ -561,36 +482,31 @@ __global__ __launch_bounds__(kWalkThreads) void ix_walk_apply_kernel(WalkArgs a,
             const unsigned long long above = lane == 63 ? 0ull : stops >> (lane + 1);
             const unsigned long long k = above ? (unsigned long long)__ffsll((long long)above) : 64ull - lane;
             IndexSlot& e = table[at];
-            atomicAdd(reinterpret_cast<unsigned long long*>(SHADOW ? &e.shadow : &e.ref),
-                      SHADOW ? k : (unsigned long long)delta * k);
+            add64(SHADOW ? &e.shadow : &e.ref, SHADOW ? k : (uint64_t)delta * k);
         }
         applied += hit;
         missed += on && !hit;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        applied += __shfl_xor(applied, o);
-        missed += __shfl_xor(missed, o);
-        if (ADDREF) skipped += __shfl_xor(skipped, o);
-    }
+    applied = wave_sum(applied);
+    missed = wave_sum(missed);
     if (ADDREF) {
+        skipped = wave_sum(skipped);
         if (lane != 0) return;
-        unsigned long long* c = reinterpret_cast<unsigned long long*>(a.acounts);
         if (MODE == kWalkAddrefCheck) {
             if (missed) {
-                atomicAdd(&c[1], (unsigned long long)missed);
+                add64(&a.acounts[1], missed);
                 atomicAdd(&a.missed[s], missed);
             }
-            if (skipped) atomicAdd(&c[2], (unsigned long long)skipped);
+            if (skipped) add64(&a.acounts[2], skipped);
         } else if (applied) {
-            atomicAdd(&c[0], (unsigned long long)applied);
+            add64(&a.acounts[0], applied);
         }
         return;
     }
     if (lane == 0) {
-        if (applied) atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[0]), (unsigned long long)applied);
+        if (applied) add64(&a.counts[0], applied);
         if (missed) {
-            atomicAdd(reinterpret_cast<unsigned long long*>(&a.counts[1]), (unsigned long long)missed);
+            add64(&a.counts[1], missed);
             if (a.missed) atomicAdd(&a.missed[s], missed);
         }
     }
@@ -623,9 +539,8 @@ __global__ __launch_bounds__(kIxThreads) void ix_addref_finish_kernel(WalkArgs a
     }
     const uint32_t nok = (uint32_t)__popcll(__ballot(ok)), nbad = (uint32_t)__popcll(__ballot(bad));
     if ((threadIdx.x & 63) == 0) {
-        unsigned long long* c = reinterpret_cast<unsigned long long*>(a.acounts);
-        if (nok) atomicAdd(&c[3], (unsigned long long)nok);
-        if (nbad) atomicAdd(&c[4], (unsigned long long)nbad);
+        if (nok) add64(&a.acounts[3], nok);
+        if (nbad) add64(&a.acounts[4], nbad);
     }
     if (s == 0 && a.acounts[5] > a.miss_cap) a.acounts[5] = a.miss_cap;  // the check pass has finished
 }
@@ -648,7 +563,7 @@ template <int KIND>
 __global__ __launch_bounds__(kRankBlock) void ix_flag_count_kernel(const IndexSlot* table, uint64_t slots,
                                                                    uint32_t* bsum, unsigned long long* flags,
                                                                    uint64_t* counts) {
-    __shared__ uint32_t lds[64];
+    __shared__ uint32_t lds[16];
     __shared__ uint32_t cat[4];
     const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
     if (KIND == kFlagMismatch && threadIdx.x < 4) cat[threadIdx.x] = 0;
@@ -668,25 +583,17 @@ __global__ __launch_bounds__(kRankBlock) void ix_flag_count_kernel(const IndexSl
     const unsigned long long m = __ballot(f);
     if ((threadIdx.x & 63) == 0) flags[i >> 6] = m;
     uint32_t total;
-    (void)block_exclusive_scan(f, lds, total);  // its barriers also order the adds to cat[]
+    (void)block_exclusive_scan_1024(f, lds, total);  // its barriers also order the adds to cat[]
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
     if (KIND == kFlagMismatch && threadIdx.x < 4 && cat[threadIdx.x])
-        atomicAdd(reinterpret_cast<unsigned long long*>(&counts[3 + threadIdx.x]), (unsigned long long)cat[threadIdx.x]);
+        add64(&counts[3 + threadIdx.x], cat[threadIdx.x]);
 }
 
 // exclusive scan of the block counts (one block); *listed = min(total, cap), *total_out = total
 __global__ __launch_bounds__(kRankBlock) void ix_flag_scan_kernel(uint32_t* bsum, uint32_t nblocks, uint64_t cap,
                                                                   uint64_t* listed, uint64_t* total_out) {
-    __shared__ uint32_t lds[64];
-    uint64_t carry = 0;
-    for (uint32_t b0 = 0; b0 < nblocks; b0 += kRankBlock) {
-        const uint32_t i = b0 + threadIdx.x;
-        const uint32_t v = i < nblocks ? bsum[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_exclusive_scan(v, lds, total);
-        if (i < nblocks) bsum[i] = (uint32_t)carry + ex;  // flagged entries <= slots <= 2^31
-        carry += total;
-    }
+    __shared__ uint32_t lds[16];
+    const uint64_t carry = block_sums_to_bases(bsum, nblocks, lds);  // flagged entries <= slots <= 2^31
     if (threadIdx.x == 0) {
         *listed = carry < cap ? carry : cap;
         if (total_out) *total_out = carry;
@@ -700,11 +607,11 @@ __global__ __launch_bounds__(kRankBlock) void ix_recount_emit_kernel(IndexSlot* 
                                                                      const unsigned long long* flags, uint64_t cap,
                                                                      uint8_t* digests, uint64_t* pos, int64_t* have,
                                                                      int64_t* want, int repair) {
-    __shared__ uint32_t lds[64];
+    __shared__ uint32_t lds[16];
     const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
     const uint32_t f = (uint32_t)(flags[i >> 6] >> (threadIdx.x & 63)) & 1u;  // set only for i < slots
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    const uint32_t ex = block_exclusive_scan_1024(f, lds, total);
     if (!f) return;  // an entry that is equal needs no repair either
     IndexSlot& s = table[i];
     const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
@@ -723,11 +630,11 @@ __global__ __launch_bounds__(kRankBlock) void ix_export_emit_kernel(const IndexS
                                                                     const uint32_t* bbase,
                                                                     const unsigned long long* flags, uint64_t cap,
                                                                     uint8_t* digests, uint64_t* pos, int64_t* ref) {
-    __shared__ uint32_t lds[64];
+    __shared__ uint32_t lds[16];
     const uint64_t i = (uint64_t)blockIdx.x * kRankBlock + threadIdx.x;
     const uint32_t f = (uint32_t)(flags[i >> 6] >> (threadIdx.x & 63)) & 1u;
     uint32_t total;
-    const uint32_t ex = block_exclusive_scan(f, lds, total);
+    const uint32_t ex = block_exclusive_scan_1024(f, lds, total);
     if (!f) return;
     const uint64_t rank = (uint64_t)bbase[blockIdx.x] + ex;
     if (rank >= cap) return;
@@ -805,7 +712,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_load_probe_kernel(const uint8_t
                 s.ref = 0;
                 s.pos = lminpos[ls];
                 gidx[ls] = (uint32_t)h;
-                atomicAdd(reinterpret_cast<unsigned long long*>(used), 1ull);
+                add64(used, 1);
                 return;
             }
             st = old;
@@ -835,7 +742,7 @@ __global__ __launch_bounds__(kIxThreads) void ix_load_apply_kernel(const uint64_
     }
     IndexSlot& s = table[g];
     const bool ok = s.pos == pos[r];
-    if (ok) atomicAdd(reinterpret_cast<unsigned long long*>(&s.ref), (unsigned long long)ref[r]);
+    if (ok) add64(&s.ref, ref[r]);
     status[r] = ok ? 0 : 1;
     if (ltab[ls] == r && s.state == stamp) s.state = kCommitted;  // the stamp must not survive the call
 }
@@ -980,7 +887,7 @@ static int check_walk(const sdfs_cdc_index* ix, const uint8_t* d_map, uint64_t n
     if (slot_bytes < kSlotFixedBytes) return fail_status(SDFS_CDC_EINVAL, "slot_bytes %u < 13", slot_bytes);
     if (!d_slot_status || !d_counts) return fail_status(SDFS_CDC_EINVAL, "null slot_status or counts");
     if (nslots && !d_map) return fail_status(SDFS_CDC_EINVAL, "null map");
-    const uint64_t parts = (pair_cap(slot_bytes, hash_len) + kWalkPart - 1) / kWalkPart;
+    const uint64_t parts = slot_parts(pair_cap(slot_bytes, hash_len));
     if (nslots >= (1ull << 31) || nslots * std::max<uint64_t>(parts, 1) >= (1ull << 32))
         return fail_status(SDFS_CDC_EINVAL, "%llu slots of %u bytes: split the image", (unsigned long long)nslots,
                            slot_bytes);
@@ -1002,7 +909,7 @@ static void launch_apply(sdfs_cdc_index* ix, hipStream_t s, const WalkArgs& a, i
 
 template <int MODE>
 static int launch_walk(sdfs_cdc_index* ix, hipStream_t s, Scratch& sc, WalkArgs a, int64_t delta) {
-    a.parts = std::max<uint32_t>(1, (pair_cap(a.slot_bytes, a.hash_len) + kWalkPart - 1) / kWalkPart);
+    a.parts = std::max<uint32_t>(1, slot_parts(pair_cap(a.slot_bytes, a.hash_len)));
     SDFS_TRY(sc.get(&a.meta, (size_t)a.nslots));
     constexpr uint32_t wpb = kWalkThreads / 64;
     hipLaunchKernelGGL(ix_walk_validate_kernel, dim3((uint32_t)((a.nslots + wpb - 1) / wpb)), dim3(kWalkThreads), 0, s,

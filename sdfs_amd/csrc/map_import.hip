@@ -1,8 +1,8 @@
 // map_import.hip — a map file of another volume becomes a file of this one (include/sdfs_import.h;
 // DESIGN.md §24).
 //
-// Slot images whose hashlocs belong to the source volume are walked by the rule of the map-file
-// walks (dedup_index.hip), their pairs laid out by image place, and after the index has said which
+// Slot images whose hashlocs belong to the source volume are accepted by slot_walk_check
+// (store_format.h), their pairs laid out by image place, and after the index has said which
 // fingerprints it holds:
 //   pairs    — validate (a wave per request), then layout (a wave per 256 pairs of a request):
 //              hash, source hashloc and the counting flag of every place;
@@ -31,50 +31,13 @@ namespace sdfs {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr uint32_t kPart = 256;  // pairs of one request a wave of the layout takes (kWalkPart of the walks)
 constexpr uint32_t kBlock = SDFS_CDC_IMPORT_BLOCK;
 constexpr uint32_t kSpan = SDFS_CDC_IMPORT_SPAN;
 constexpr uint32_t kNone = SDFS_CDC_IMPORT_NONE;
-constexpr uint32_t kUnsorted = 0x80000000u;  // meta: the image's pos values are not strictly ascending
 static_assert(kBlock == 1024, "a scan block is 1024 threads, 16 waves");
 static_assert(kSpan % 16 == 0, "a span is whole vectors");
 
 using Work = sdfs_cdc_import_work;
-
-__device__ __forceinline__ void add64(uint64_t* p, uint64_t v) {
-    atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
-// 64-lane sum, the result in every lane
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        if constexpr (sizeof(T) == 8) v += (T)__shfl_xor((unsigned long long)v, o);
-        else v += __shfl_xor(v, o);
-    }
-    return v;
-}
-
-// A block of 1024 threads: the sum over the threads before this one; total = the block's sum.
-// lds holds 16 entries and may be used again after the call returns.
-template <typename T>
-__device__ __forceinline__ T block_exclusive_1024(T v, T* lds, T& total) {
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const T inc = wave_inclusive_scan(v, lane);
-    if (lane == 63) lds[wv] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        const T s = lds[k];
-        if (k < wv) before += s;
-        all += s;
-    }
-    __syncthreads();
-    total = all;
-    return before + inc - v;
-}
 
 // ---------------------------------------------------------------------------------------- pairs
 
@@ -86,44 +49,24 @@ struct PairsArgs {
     uint32_t pair_stride;
     uint32_t parts;  // waves per request in the layout
     Work w;
-    uint32_t* meta;  // [nreq] scratch: pairs | kUnsorted
+    uint32_t* meta;  // [nreq] scratch: slot_meta
 };
 
-// a wave per request: the rule of ix_walk_validate_kernel (every branch is wave-uniform)
+// a wave per request (every branch is wave-uniform)
 __global__ __launch_bounds__(kThreads) void imp_validate_kernel(PairsArgs a) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t r = (uint64_t)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
     if (r >= a.nreq) return;
-    const uint32_t hl = a.hash_len;
-    const uint8_t* img = a.req + r * a.slot_bytes;
-    const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
-    uint32_t status = 0, n = 0;
-    if (zlen > 0) {
-        if (slot_need((uint32_t)zlen, hl) > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;
-        else n = (uint32_t)zlen;
-    }
-    bool neg = false, unsorted = false;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint8_t* q = pair_fields(img, i, hl);
-        const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
-        neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
-                (int32_t)get_be32(q + kPairNlenAt)) < 0;
-        if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hl) + kPairPosAt) >= ps;
-    }
-    if (__ballot(neg) != 0) {  // HashLocPair.checkCorrupt
-        status = SDFS_CDC_READ_CORRUPT;
-        n = 0;
-    }
-    unsorted = __ballot(unsorted) != 0;
+    const SlotWalk w = slot_walk_check(a.req + r * a.slot_bytes, a.slot_bytes, a.hash_len, lane);
     if (lane == 0) {
-        a.w.status[r] = status;
-        a.w.req_pairs[r] = n;
+        a.w.status[r] = w.status;
+        a.w.req_pairs[r] = w.n;
         a.w.req_missed[r] = 0;
-        a.meta[r] = n | (n && unsorted ? kUnsorted : 0u);
+        a.meta[r] = slot_meta(w);
     }
 }
 
-// a wave per (request, kPart places): every place of the request is written, the ones past its
+// a wave per (request, kSlotPart places): every place of the request is written, the ones past its
 // pairs with zeros.  HW: words of a pair's hash (8 = SHA-256, 4 = MD5).
 template <int HW>
 __global__ __launch_bounds__(kThreads) void imp_layout_kernel(PairsArgs a) {
@@ -132,9 +75,9 @@ __global__ __launch_bounds__(kThreads) void imp_layout_kernel(PairsArgs a) {
     const uint64_t r = unit / a.parts;
     if (r >= a.nreq) return;  // wave-uniform
     const uint32_t meta = a.meta[r];
-    const uint32_t n = meta & ~kUnsorted;  // <= pair_cap(slot_bytes) <= pair_stride
-    const uint32_t i0 = (uint32_t)(unit % a.parts) * kPart;
-    const uint32_t i1 = min(a.pair_stride, i0 + kPart);
+    const uint32_t n = slot_meta_pairs(meta);  // <= pair_cap(slot_bytes) <= pair_stride
+    const uint32_t i0 = (uint32_t)(unit % a.parts) * kSlotPart;
+    const uint32_t i1 = min(a.pair_stride, i0 + kSlotPart);
     constexpr uint32_t hl = HW * 4;
     const uint8_t* img = a.req + r * a.slot_bytes;
     for (uint32_t i = i0 + lane; i < i1; i += 64) {
@@ -143,18 +86,8 @@ __global__ __launch_bounds__(kThreads) void imp_layout_kernel(PairsArgs a) {
         uint64_t hashloc = 0;
         bool on = false;
         if (i < n) {
-            uint32_t w[HW + 2];  // hash | BE64 hashloc
-            load_words(slot_pair(img, i, hl), w);
-            ka = make_uint4(w[0], w[1], w[2], w[3]);
-            if (HW == 8) kb = make_uint4(w[HW - 4], w[HW - 3], w[HW - 2], w[HW - 1]);
-            hashloc = (uint64_t)__builtin_bswap32(w[HW]) << 32 | __builtin_bswap32(w[HW + 1]);
-            on = true;
-            if (meta & kUnsorted) {  // TreeMap.put: a later pair with the same pos replaces this one
-                const uint32_t ps = get_be32(pair_fields(img, i, hl) + kPairPosAt);
-                bool dead = false;
-                for (uint32_t j = i + 1; j < n; j++) dead |= get_be32(pair_fields(img, j, hl) + kPairPosAt) == ps;
-                on = !dead;
-            }
+            load_pair_key<HW>(img, i, ka, kb, hashloc);
+            on = !(slot_meta_unsorted(meta) && pair_superseded(img, i, n, hl));
         }
         uint4* h = reinterpret_cast<uint4*>(a.w.hashes + place * 32);
         h[0] = ka;
@@ -247,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void imp_dir_count_kernel(PlanArgs a) {
     uint32_t on, raw, sl;
     uint64_t d, p;
     dir_terms(a, k, on, raw, sl, d, p);
-    const uint64_t c = wave_sum<uint64_t>(on), sd = wave_sum(d), sp = wave_sum(p);
+    const uint64_t c = wave_sum<uint64_t>(on), sd = wave_sum(d), sp = wave_sum(p);  // sums alone: no scan
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) {
         lds[0][wv] = c;
@@ -271,24 +204,9 @@ __global__ __launch_bounds__(kBlock) void imp_dir_count_kernel(PlanArgs a) {
 // scan: one block over the block sums, which become the sums before each block; the totals
 __global__ __launch_bounds__(kBlock) void imp_dir_scan_kernel(PlanArgs a) {
     __shared__ uint64_t lds[16];
-    uint64_t cc = 0, cd = 0, cp = 0;
-    for (uint32_t b0 = 0; b0 < a.nblocks; b0 += kBlock) {
-        const uint32_t b = b0 + threadIdx.x;
-        const bool in = b < a.nblocks;
-        const uint64_t vc = in ? a.bcnt[b] : 0, vd = in ? a.bdst[b] : 0, vp = in ? a.bplain[b] : 0;
-        uint64_t tc, td, tp;
-        const uint64_t ec = block_exclusive_1024(vc, lds, tc);
-        const uint64_t ed = block_exclusive_1024(vd, lds, td);
-        const uint64_t ep = block_exclusive_1024(vp, lds, tp);
-        if (in) {
-            a.bcnt[b] = (uint32_t)(cc + ec);
-            a.bdst[b] = cd + ed;
-            a.bplain[b] = cp + ep;
-        }
-        cc += tc;
-        cd += td;
-        cp += tp;
-    }
+    const uint64_t cc = block_sums_to_bases(a.bcnt, a.nblocks, reinterpret_cast<uint32_t*>(lds));
+    const uint64_t cd = block_sums_to_bases(a.bdst, a.nblocks, lds);
+    const uint64_t cp = block_sums_to_bases(a.bplain, a.nblocks, lds);
     if (threadIdx.x == 0) {
         *a.fetch_count = (uint32_t)cc;
         a.total_bytes[0] = cd;
@@ -299,22 +217,20 @@ __global__ __launch_bounds__(kBlock) void imp_dir_scan_kernel(PlanArgs a) {
 
 // assign: the wanted entries of a block get their fetches
 __global__ __launch_bounds__(kBlock) void imp_dir_assign_kernel(PlanArgs a) {
-    __shared__ uint64_t lds[16];
+    __shared__ uint64_t lds[3][16];
     const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     uint32_t on, raw, sl;
     uint64_t d, p;
     dir_terms(a, k, on, raw, sl, d, p);
-    uint64_t tc, td, tp;
-    const uint64_t ec = block_exclusive_1024<uint64_t>(on, lds, tc);
-    const uint64_t ed = block_exclusive_1024(d, lds, td);
-    const uint64_t ep = block_exclusive_1024(p, lds, tp);
+    uint64_t ex[3] = {on, d, p}, total[3];
+    block_exclusive_scan_1024(ex, lds, total);
     if (on) {
-        const uint32_t f = a.bcnt[blockIdx.x] + (uint32_t)ec;
+        const uint32_t f = a.bcnt[blockIdx.x] + (uint32_t)ex[0];
         a.src_off[f] = a.store_off[k];
         a.src_len[f] = sl;
-        a.dst_off[f] = a.bdst[blockIdx.x] + ed;
+        a.dst_off[f] = a.bdst[blockIdx.x] + ex[1];
         a.dst_cap[f] = raw;
-        if (a.plain_off) a.plain_off[f] = a.bplain[blockIdx.x] + ep;
+        if (a.plain_off) a.plain_off[f] = a.bplain[blockIdx.x] + ex[2];
         a.mark[k] = f;
     }
     const uint64_t rawsum = wave_sum<uint64_t>(raw);
@@ -378,7 +294,7 @@ __device__ __forceinline__ bool emits(const RecArgs& a, uint64_t place) {
     return place < a.places && a.w.counting[place] && a.w.status[place / a.pair_stride] == 0;
 }
 
-// count: per block of kBlock places
+// count: per block of kBlock places (two ballots, no scan: see block_exclusive_scan_1024)
 __global__ __launch_bounds__(kBlock) void imp_rec_count_kernel(RecArgs a) {
     __shared__ uint32_t lds[2][16];
     const uint64_t place = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -403,18 +319,11 @@ __global__ __launch_bounds__(kBlock) void imp_rec_count_kernel(RecArgs a) {
 
 // scan: one block over the block sums
 __global__ __launch_bounds__(kBlock) void imp_rec_scan_kernel(RecArgs a) {
-    __shared__ uint64_t lds[16];
-    uint64_t carry = 0, held = 0;
-    for (uint32_t b0 = 0; b0 < a.nblocks; b0 += kBlock) {
-        const uint32_t b = b0 + threadIdx.x;
-        const bool in = b < a.nblocks;
-        uint64_t total, th;
-        const uint64_t ex = block_exclusive_1024<uint64_t>(in ? a.bsum[b] : 0, lds, total);
-        (void)block_exclusive_1024<uint64_t>(in ? a.bheld[b] : 0, lds, th);
-        if (in) a.bsum[b] = (uint32_t)(carry + ex);
-        carry += total;
-        held += th;
-    }
+    __shared__ uint32_t lds[16];
+    const uint64_t carry = block_sums_to_bases(a.bsum, a.nblocks, lds);
+    uint32_t h = 0, held;  // held pairs <= places < 2^31
+    for (uint32_t b = threadIdx.x; b < a.nblocks; b += kBlock) h += a.bheld[b];
+    (void)block_exclusive_scan_1024(h, lds, held);
     if (threadIdx.x == 0) {
         *a.count = (uint32_t)carry;
         a.w.counts[0] = carry;
@@ -428,7 +337,7 @@ __global__ __launch_bounds__(kBlock) void imp_rec_assign_kernel(RecArgs a) {
     const uint64_t place = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool on = emits(a, place);
     uint32_t total;
-    const uint32_t ex = block_exclusive_1024<uint32_t>(on ? 1u : 0u, lds, total);
+    const uint32_t ex = block_exclusive_scan_1024<uint32_t>(on ? 1u : 0u, lds, total);
     if (place >= a.places) return;
     if (!on) {
         a.w.pair_rec[place] = kNone;
@@ -583,7 +492,7 @@ int sdfs_cdc_import_pairs(int device, const uint8_t* d_req, uint64_t nreq, uint3
     SDFS_TRY(hipMemsetAsync(w->counts, 0, 8 * sizeof(uint64_t), s));
     if (nreq == 0) return SDFS_CDC_OK;
     Scratch sc(s);
-    PairsArgs a{d_req, nreq, slot_bytes, hash_len, pair_stride, (pair_stride + kPart - 1) / kPart, *w, nullptr};
+    PairsArgs a{d_req, nreq, slot_bytes, hash_len, pair_stride, slot_parts(pair_stride), *w, nullptr};
     SDFS_TRY(sc.get(&a.meta, (size_t)nreq));
     hipLaunchKernelGGL(imp_validate_kernel, grid_of(nreq, kThreads / 64), dim3(kThreads), 0, s, a);
     const dim3 g = grid_of(nreq * a.parts, kThreads / 64);

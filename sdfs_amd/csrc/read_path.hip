@@ -85,30 +85,15 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
     const uint32_t b = blockIdx.x;
     const uint8_t* img = a.map + (uint64_t)b * a.slot_bytes;
     const uint32_t hl = a.hash_len;
-    const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
-    uint32_t status = 0, n = 0;
-    if (zlen > 0) {
-        if (slot_need((uint32_t)zlen, hl) > a.slot_bytes) status = SDFS_CDC_READ_CORRUPT;  // BufferUnderflowException
-        else n = (uint32_t)zlen;
-    }
-    bool neg = false, unsorted = false;
-    for (uint32_t i = lane; i < n; i += 64) {
-        const uint8_t* q = pair_fields(img, i, hl);
-        const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
-        neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
-                (int32_t)get_be32(q + kPairNlenAt)) < 0;
-        if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hl) + kPairPosAt) >= ps;
-    }
-    if (wave_any(neg)) {  // HashLocPair.checkCorrupt
-        status = SDFS_CDC_READ_CORRUPT;
-        n = 0;
-    }
+    const SlotWalk w = slot_walk_check(img, a.slot_bytes, hl, lane);
+    const uint32_t status = w.status, n = w.n;
     const uint64_t base = (uint64_t)b * a.p.cap;
     uint32_t count = n;
-    if (!wave_any(unsorted)) {
+    if (!w.unsorted) {
         for (uint32_t i = lane; i < n; i += 64) put_pair(a, slot_pair(img, i, hl), base + i);
     } else {
-        // TreeMap.put per pair in image order: a later pair with the same pos replaces the earlier
+        // tmp_dead[i] = pair_superseded(img, i, n, hl), from a copy of the pos values that the rank
+        // below reads again
         for (uint32_t i = lane; i < n; i += 64)
             a.tmp_pos[base + i] = (int32_t)get_be32(pair_fields(img, i, hl) + kPairPosAt);
         __syncthreads();
@@ -128,9 +113,7 @@ __global__ __launch_bounds__(64) void map_parse_kernel(ParseArgs a) {
             for (uint32_t j = 0; j < n; j++) rank += !a.tmp_dead[base + j] && a.tmp_pos[base + j] < ps;
             put_pair(a, slot_pair(img, i, hl), base + rank);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) live += __shfl_xor(live, o);
-        count = live;
+        count = wave_sum(live);
     }
     if (lane == 0) {
         a.p.counts[b] = count;
@@ -191,7 +174,8 @@ __global__ __launch_bounds__(64) void plan_mark_kernel(PlanArgs a) {
     }
 }
 
-// one block: rank the marked directory entries and lay out their fetches.  The directory is
+// one block: rank the marked directory entries and lay out their fetches (its own scan text: see
+// block_exclusive_scan_1024).  The directory is
 // walked in tiles of 1024 entries (coalesced), each tile scanned wave by wave, the running totals
 // carried from tile to tile.
 __global__ __launch_bounds__(1024) void plan_scan_kernel(PlanArgs a) {
@@ -744,8 +728,7 @@ __global__ __launch_bounds__(64) void verify_compare_kernel(VerifyArgs a) {
         a.pair_bad[base + i] = (uint8_t)bad;
         nbad += bad;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) nbad += __shfl_xor(nbad, o);
+    nbad = wave_sum(nbad);
     if (lane == 0) a.bad_count[b] = nbad;
 }
 

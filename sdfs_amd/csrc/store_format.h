@@ -2,8 +2,8 @@
 // else (host + device).  Not part of the C-ABI.
 //
 //   slot image     SparseDataChunk.getBytes (SparseDataChunk.java:295-318, HashLocPair.asArray
-//                  HashLocPair.java:49-59); written by map_emit.hip and map_merge.hip, parsed by
-//                  read_path.hip
+//                  HashLocPair.java:49-59); written by map_emit.hip and map_merge.hip; accepted by
+//                  slot_walk_check for read_path.hip, dedup_index.hip and map_import.hip
 //   .map image     SimpleByteArrayLongMap's file (SimpleByteArrayLongMap.java:198-261,427-498,
 //                  509-539); written by archive_pack.hip, read back by store_open.hip
 //   archive record HashBlobArchive.putChunk (HashBlobArchive.java:1399-1411); laid out and packed by
@@ -18,6 +18,7 @@
 
 #include "../../include/sdfs_archive.h"
 #include "../../include/sdfs_lz4_stream.h"
+#include "../../include/sdfs_read.h"
 
 namespace sdfs {
 namespace {  // internal linkage: nothing here joins the libraries' exported symbols
@@ -85,6 +86,71 @@ __device__ __forceinline__ void load_words(const uint8_t* p, uint32_t (&w)[N]) {
 #pragma unroll
     for (int i = 0; i < N; i++) w[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], r);
 }
+
+// How an image is accepted (SparseDataChunk's constructor; one wave, every branch wave-uniform):
+// zlen <= 0 holds no pairs; an image that needs more than slot_bytes is CORRUPT; a negative len,
+// pos, offset or nlen is CORRUPT with no pairs (HashLocPair.checkCorrupt); unsorted = some pos is
+// not above its predecessor's.  A lane loads a pos only for its own pairs and the ones before them.
+struct SlotWalk {
+    uint32_t status;  // 0 or SDFS_CDC_READ_CORRUPT
+    uint32_t n;       // pairs to walk
+    bool unsorted;    // only with n > 0
+};
+
+__device__ __forceinline__ SlotWalk slot_walk_check(const uint8_t* img, uint32_t slot_bytes, uint32_t hash_len,
+                                                    uint32_t lane) {
+    SlotWalk w{0, 0, false};
+    const int32_t zlen = (int32_t)get_be32(img + kSlotCountAt);
+    if (zlen > 0) {
+        if (slot_need((uint32_t)zlen, hash_len) > slot_bytes) w.status = SDFS_CDC_READ_CORRUPT;  // BufferUnderflowException
+        else w.n = (uint32_t)zlen;
+    }
+    bool neg = false, unsorted = false;
+    for (uint32_t i = lane; i < w.n; i += 64) {
+        const uint8_t* q = pair_fields(img, i, hash_len);
+        const int32_t ps = (int32_t)get_be32(q + kPairPosAt);
+        neg |= ((int32_t)get_be32(q + kPairLenAt) | ps | (int32_t)get_be32(q + kPairOffsetAt) |
+                (int32_t)get_be32(q + kPairNlenAt)) < 0;
+        if (i > 0) unsorted |= (int32_t)get_be32(pair_fields(img, i - 1, hash_len) + kPairPosAt) >= ps;
+    }
+    if (__ballot(neg) != 0) {
+        w.status = SDFS_CDC_READ_CORRUPT;
+        w.n = 0;
+    }
+    w.unsorted = w.n && __ballot(unsorted) != 0;
+    return w;
+}
+
+// TreeMap.put per pair in image order: pair i of an unsorted image of n pairs does not count when
+// a later pair has the same pos
+__device__ __forceinline__ bool pair_superseded(const uint8_t* img, uint32_t i, uint32_t n, uint32_t hash_len) {
+    const uint32_t ps = get_be32(pair_fields(img, i, hash_len) + kPairPosAt);
+    bool dead = false;
+    for (uint32_t j = i + 1; j < n; j++) dead |= get_be32(pair_fields(img, j, hash_len) + kPairPosAt) == ps;
+    return dead;
+}
+
+// The hash of pair i as two key words (kb zero for HW = 4) and its BE64 hashloc, by aligned loads
+// (pairs start at odd byte offsets).  HW: words of a pair's hash (8 = SHA-256, 4 = MD5).
+template <int HW>
+__device__ __forceinline__ void load_pair_key(const uint8_t* img, uint32_t i, uint4& ka, uint4& kb, uint64_t& hashloc) {
+    uint32_t w[HW + 2];  // hash | BE64 hashloc
+    load_words(slot_pair(img, i, HW * 4), w);
+    ka = make_uint4(w[0], w[1], w[2], w[3]);
+    kb = HW == 8 ? make_uint4(w[HW - 4], w[HW - 3], w[HW - 2], w[HW - 1]) : make_uint4(0, 0, 0, 0);
+    hashloc = (uint64_t)__builtin_bswap32(w[HW]) << 32 | __builtin_bswap32(w[HW + 1]);
+}
+
+// What a walk keeps per image between its check and its passes over the pairs: n, and the unsorted
+// flag.  A wave of such a pass takes kSlotPart pairs of one image.
+constexpr uint32_t kSlotUnsorted = 0x80000000u;
+constexpr uint32_t kSlotPart = 256;
+
+__device__ __forceinline__ uint32_t slot_meta(const SlotWalk& w) { return w.n | (w.unsorted ? kSlotUnsorted : 0u); }
+__device__ __forceinline__ uint32_t slot_meta_pairs(uint32_t meta) { return meta & ~kSlotUnsorted; }
+__device__ __forceinline__ bool slot_meta_unsorted(uint32_t meta) { return (meta & kSlotUnsorted) != 0; }
+
+__host__ __device__ inline uint32_t slot_parts(uint32_t pairs) { return (pairs + kSlotPart - 1) / kSlotPart; }
 
 // pair i from its six fields (byte stores: records start at odd offsets)
 __device__ __forceinline__ void put_pair_record(uint8_t* img, uint32_t i, uint32_t hash_len, const uint8_t* hash,

@@ -174,21 +174,19 @@ __global__ __launch_bounds__(256) void store_count_kernel(ScanArgs2 a) {
 
 // arc_first = the exclusive prefix of cnt; count, status (one block)
 __global__ __launch_bounds__(1024) void store_prefix_kernel(ScanArgs2 a) {
-    __shared__ uint64_t part[1024];
+    __shared__ uint64_t lds[16];
     const uint32_t t = threadIdx.x, n = a.im.n_arc;
     uint32_t a0, a1;
     block_run_1024(n, a0, a1);
-    uint64_t sum = 0;
+    uint64_t sum = 0, total;
     for (uint32_t i = a0; i < a1; i++) sum += a.cnt[i];
-    const uint64_t incl = block_inclusive_scan_1024(sum, part);
-    const uint64_t total = part[1023];
+    uint64_t run = block_exclusive_scan_1024(sum, lds, total);
     const bool fits = total <= a.r.n_cap;
     if (t == 0) {
         *a.r.count = (uint32_t)min(total, (uint64_t)UINT32_MAX);
         *a.r.status = fits ? 0 : SDFS_CDC_STORE_ECAP;
     }
     if (!fits) return;
-    uint64_t run = incl - sum;
     for (uint32_t i = a0; i < a1; i++) {
         a.o.arc_first[i] = (uint32_t)run;
         run += a.cnt[i];
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(256) void store_dir_claim_kernel(DirArgs a) {
     int why = 0;
     const uint64_t k = dir_entry(a, r, why);
     if (k < a.n_store) atomicMin(&a.owner[k], (uint32_t)r);
-    else atomicAdd(reinterpret_cast<unsigned long long*>(&a.info[why]), 1ull);
+    else add64(&a.info[why], 1);
 }
 
 __global__ __launch_bounds__(256) void store_dir_write_kernel(DirArgs a) {
@@ -364,7 +362,7 @@ __global__ __launch_bounds__(256) void store_dir_write_kernel(DirArgs a) {
     if (i < n) {
         int why = 0;
         const uint64_t k = dir_entry(a, i, why);
-        if (k < a.n_store && a.owner[k] != (uint32_t)i) atomicAdd(reinterpret_cast<unsigned long long*>(&a.info[2]), 1ull);
+        if (k < a.n_store && a.owner[k] != (uint32_t)i) add64(&a.info[2], 1);
     }
 }
 

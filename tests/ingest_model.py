@@ -46,6 +46,29 @@ def counting_pairs(img: bytes, slot_bytes: int, hash_len: int):
     return st, [(i, h, loc) for i, h, loc, pos in recs if last[pos] == i]
 
 
+def plan_chunks(entries, blob_len: int, chunk_length: int, stage_cap=None):
+    """What the plan decides from the client's numbers alone.  entries: [(hash, off, len, raw_len,
+    compressed)] -> (status[], stage_off[], [(off, len, stage_off, raw_len, entry)] of the entries to
+    decode, in entry order).  The places are the prefix of raw_len over every entry whose numbers
+    are in bounds, whether or not it still fits the staging area."""
+    status, stage_off, decode, staged = [], [], [], 0
+    for i, (_, off, ln, raw, comp) in enumerate(entries):
+        st, at = 0, 0
+        if ln == 0:
+            st = EMPTY
+        elif raw == 0 or raw > chunk_length or off + ln > blob_len or (not comp and ln != raw):
+            st = EBOUNDS
+        else:
+            at, staged = staged, staged + raw
+            if stage_cap is not None and staged > stage_cap:
+                st = EBOUNDS
+        status.append(st)
+        stage_off.append(0 if st else at)
+        if not st and comp:
+            decode.append((off, ln, at, raw, i))
+    return status, stage_off, decode
+
+
 class IngestModel:
     """index: an ``IndexModel``; digest(chunk) -> the fingerprint (for verify); stored_len(chunk) ->
     the length of the record the store keeps for it."""
@@ -61,18 +84,11 @@ class IngestModel:
         """entries: [(hash, off, len, raw_len, compressed)] over ``blob`` ->
         (inserted[], pos[], stored_len[], status[])."""
         inserted, pos, stored, status = [], [], [], []
-        rank = staged = 0
-        for h, off, ln, raw, comp in entries:
-            st, chunk = 0, None
-            if ln == 0:
-                st = EMPTY
-            elif raw == 0 or raw > self.cl or off + ln > len(blob) or (not comp and ln != raw):
-                st = EBOUNDS
-            elif stage_cap is not None and staged + raw > stage_cap:
-                staged += raw  # the places are the prefix over every entry that got this far
-                st = EBOUNDS
-            else:
-                staged += raw
+        rank = 0
+        planned = plan_chunks(entries, len(blob), self.cl, stage_cap)[0]
+        for (h, off, ln, raw, comp), st in zip(entries, planned):
+            chunk = None
+            if not st:
                 payload = blob[off: off + ln]
                 if comp:
                     r = Z.decode(payload, raw)

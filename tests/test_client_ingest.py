@@ -20,7 +20,7 @@ from tests import mapfile_model as MM
 from tests import read_model as R
 
 PB = 1 << 33
-WALK_PART = 256  # kWalkPart of dedup_index.hip: pairs of one slot a wave of the walks takes
+WALK_PART = 256  # kSlotPart of store_format.h: pairs of one slot a wave of the walks takes
 
 
 def H(i, hl=32):

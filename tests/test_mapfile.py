@@ -18,16 +18,13 @@ import pytest
 from sdfs_amd import _lib, mapfile
 from tests import mapfile_model as MM
 from tests import read_model as R
+from tests.slot_images import digest as _digest, held as _held, seeded_image as _seeded_image
 
 CL = 262144
 
 
 def H(i, hl=32):
     return (b"h%07d" % i).ljust(hl, b"\x5a")
-
-
-def _digest(rng, hl=32):
-    return bytes(rng.getrandbits(8) for _ in range(hl))
 
 
 def _pairs(items, step=100):
@@ -75,47 +72,6 @@ def test_model_hand_worked_recount():
     assert m.export() == sorted([(a, 1, 2), (b, 2, 2), (c, 3, 1), (d, 4, 0)])
     assert m.recount(imgs, sb, 32)[0] == [5, 1, 0, 0, 0, 1, 4, 0]
     assert m.sweep() == [(d, 4)]
-
-
-def _seeded_image(rng, held, hl, cap):
-    """One image in IMAGE order and its slot kind; ``held``: [(digest, pos)] the index holds."""
-    kind = rng.choice(["plain"] * 6 + ["zero", "zlen0", "full", "over", "negzlen", "negfield", "repeat"])
-    if kind == "zero":
-        return b"", kind
-
-    def pair(i):
-        u = rng.random()
-        d, loc = rng.choice(held)
-        if u < 0.1:
-            d = _digest(rng, hl)       # not held
-        elif u < 0.2:
-            loc ^= 0x10000             # the wrong archive
-        return (d[:hl], loc, 10, i * 10, 0, 10)
-
-    n = {"zlen0": 0, "full": cap, "over": cap}.get(kind, rng.randint(1, cap))
-    pairs = [pair(i) for i in range(n)]
-    zlen = None
-    if kind == "over":
-        zlen = cap + 1
-    elif kind == "negzlen":
-        zlen = -rng.randint(1, 5)
-    elif kind == "negfield":
-        p = list(pairs[-1])
-        p[rng.choice([2, 3, 4, 5])] = -rng.randint(1, 1 << 30)
-        pairs[-1] = tuple(p)
-    elif kind == "repeat" and n >= 2:
-        for _ in range(rng.randint(1, 3)):
-            i, j = rng.sample(range(n), 2)
-            p = list(pairs[i])
-            p[3] = pairs[j][3]
-            pairs[i] = tuple(p)
-        rng.shuffle(pairs)
-    return R.build_image(pairs, flags=rng.randrange(256), doop=rng.randrange(1 << 20), zlen=zlen), kind
-
-
-def _held(rng, n, hl, pos0=0):
-    """n entries; positions 0 and 1 are real positions here (pos_base = 0)."""
-    return [(_digest(rng, hl).ljust(32, b"\0"), pos0 + i) for i in range(n)]
 
 
 @pytest.mark.parametrize("hl", [32, 16])
